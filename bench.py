@@ -11,6 +11,10 @@ One step = forward + CTC + backward + (DDP all-reduce) + clip + Adam over one B 
     torchrun --nproc-per-node N ... bench.py --gpus N   (one rank per GPU, RCCL)
 
 Prints ONE JSON line on rank 0.  value = frames processed by all ranks / max-over-ranks time.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what takes
+runs of its own: the CPU baselines (cpu_baseline) and, under --graph on, the eager steps behind
+the per-kernel timings.  --dump-outputs DIR writes what the last timed step returned as .npy.
 """
 import argparse
 import json
@@ -53,7 +57,15 @@ def parse():
     ap.add_argument("--bucket-mb", type=float, default=8.0,
                     help="DDP gradient bucket size: ~one layer (7.3 MB fp32) per bucket, so each "
                          "layer's all-reduce overlaps the backward of the layers below it")
-    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines "
+                         "(--cpu-baseline) and, with --graph on, the eager steps that time each kernel")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one handed its caller (loss, "
+                         "carried encoder state, updated parameters) as DIR/<name>.npy (float32 / "
+                         "float64; beyond 48 MB a fixed seeded sample of each large array)")
+    ap.add_argument("--cpu-baseline", choices=["on", "off"], default="on",
+                    help="with --full: the CPU baselines of the ctc workload")
     ap.add_argument("--cpu-seq", type=int, default=1500,
                     help="T of the bounded CPU sample (default: one full C2 segment, ~10 s)")
     ap.add_argument("--tunableop", choices=["on", "off"], default="on",
@@ -317,6 +329,41 @@ def c1_lstm_baseline(seconds=4.0):
                       f"{dt:.1f} s, torch CPU threads={torch.get_num_threads()}"}
 
 
+DUMP_BUDGET = 48 << 20   # bytes of fp32 a dump may hold in full; beyond it large arrays are sampled
+
+
+def state_leaves(state, prefix="state"):
+    """(name, tensor) for every tensor of a carried encoder state (tensor, list / tuple or dict)."""
+    if torch.is_tensor(state):
+        return [(prefix, state)]
+    if isinstance(state, dict):
+        return [x for k in sorted(state, key=str) for x in state_leaves(state[k], f"{prefix}.{k}")]
+    if isinstance(state, (list, tuple)):
+        return [x for i, v in enumerate(state) for x in state_leaves(v, f"{prefix}.{i}")]
+    return []
+
+
+def dump_outputs(path, loss, state, named_params):
+    """--dump-outputs: what the last timed step handed its caller, one DIR/<name>.npy each: the
+    loss (float64), the carried encoder state and the parameters as the step left them (float32).
+    When they exceed DUMP_BUDGET every array above 4096 elements keeps the same fraction of its
+    elements, at indices drawn once from a generator seeded by the array's position (the same
+    indices in every run of the same arguments), so the dump stays below 64 MB."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), loss.detach().double().cpu().numpy().reshape(-1))
+    arrays = [(n, t.detach()) for n, t in state_leaves(state)] + \
+             [("param." + n, p.detach()) for n, p in named_params]
+    big = sum(t.numel() for _, t in arrays if t.numel() > 4096)
+    small = sum(t.numel() for _, t in arrays) - big
+    frac = min(1.0, max(0.0, DUMP_BUDGET / 4 - small) / max(1, big))
+    for k, (name, t) in enumerate(arrays):
+        a = t.float().cpu().numpy()
+        if frac < 1.0 and a.size > 4096:
+            idx = np.sort(np.random.default_rng(k).integers(0, a.size, max(1, int(a.size * frac))))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name.replace("/", "_") + ".npy"), np.ascontiguousarray(a))
+
+
 def free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -522,7 +569,13 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     last_loss = float(loss.item())
-    if graphed is not None and args.timing_steps > 0:
+    if args.dump_outputs and rank == 0:
+        named = list(model.named_parameters())
+        if tkw.get("joiner") is not None:
+            named += [("joiner." + n, p) for n, p in tkw["joiner"].named_parameters()]
+        dump_outputs(args.dump_outputs, loss, None if graphed is not None else trainer.encoder_state,
+                     named)
+    if graphed is not None and args.timing_steps > 0 and args.full:
         # a replay records no per-launch events: the kernel timings come from eager steps of the
         # same segments right after the timed region (same kernels, same shapes)
         for p in graphed.params:
@@ -602,7 +655,7 @@ def main():
     value = frames / dt
     ms = dt / args.steps * 1e3
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_baseline == "on" and args.workload == "ctc":
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline == "on" and args.workload == "ctc":
         cpu = cpu_baseline(args)
     if rank == 0:
         gf = gemm_flops_per_frame(args)
@@ -626,7 +679,8 @@ def main():
             "kernel_timing": (f"HIP events on the launch stream, last {min(args.timing_steps, args.steps)} "
                               "timed steps") if graphed is None else
                              (f"HIP events on the launch stream, {args.timing_steps} eager steps "
-                              "right after the timed graph replays"),
+                              "right after the timed graph replays") if args.full else
+                             "none (a graph replay records no events; --full times eager steps)",
             "launch": "hip-graph replay per segment (forward + backward), clip + Adam eager"
                       if graphed is not None else "eager",
             "gemm_TFLOPs_effective": round(gemm_tflops / world, 1) if gemm_tflops else None,

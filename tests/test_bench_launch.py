@@ -1,5 +1,5 @@
 """bench.py's --gpus launcher: environment plumbing with a stub worker that never touches HIP,
-and the loud failures (bad --gpus, WORLD_SIZE mismatch)."""
+the loud failures (bad --gpus, WORLD_SIZE mismatch), and the files --dump-outputs writes."""
 import json
 import os
 import subprocess
@@ -45,6 +45,37 @@ def test_bad_gpus_exits_nonzero(argv, env):
                        capture_output=True, text=True, timeout=120)
     assert p.returncode != 0
     assert "--gpus" in p.stderr
+
+
+def test_dump_outputs_files_and_seeded_sample(tmp_path, monkeypatch):
+    """--dump-outputs: loss as float64, state leaves and parameters as float32, one .npy each;
+    past the budget every large array keeps the same seeded sample in every run."""
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    w = torch.randn(100, 200, generator=g)
+    small = torch.randn(7, generator=g, dtype=torch.float64).to(torch.bfloat16)
+    state = {"b": (torch.ones(2, 3), [torch.zeros(4)]), "a": torch.full((2,), 5.0)}
+    loss = torch.tensor(1.25)
+    bench.dump_outputs(str(tmp_path / "x"), loss, state, [("enc.w", w), ("enc.b", small)])
+    got = {f: np.load(tmp_path / "x" / f) for f in sorted(os.listdir(tmp_path / "x"))}
+    assert sorted(got) == ["loss.npy", "param.enc.b.npy", "param.enc.w.npy", "state.a.npy",
+                           "state.b.0.npy", "state.b.1.0.npy"]
+    assert got["loss.npy"].dtype == np.float64 and got["loss.npy"].tolist() == [1.25]
+    assert all(a.dtype == np.float32 for f, a in got.items() if f != "loss.npy")
+    assert np.array_equal(got["param.enc.w.npy"], w.numpy())
+    assert np.array_equal(got["param.enc.b.npy"], small.float().numpy())
+    assert np.array_equal(got["state.a.npy"], [5.0, 5.0]) and got["state.b.0.npy"].shape == (2, 3)
+    # a budget of 10,000 floats: the 20,000-element weight is sampled, the small arrays are whole
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 40000)
+    for d in ("y", "z"):
+        bench.dump_outputs(str(tmp_path / d), loss, state, [("enc.w", w), ("enc.b", small)])
+    y, z = np.load(tmp_path / "y" / "param.enc.w.npy"), np.load(tmp_path / "z" / "param.enc.w.npy")
+    assert y.ndim == 1 and 0 < y.size < w.numel() and np.array_equal(y, z)
+    assert np.isin(y, w.numpy()).all()
+    assert np.array_equal(np.load(tmp_path / "y" / "param.enc.b.npy"), small.float().numpy())
+    total = sum(os.path.getsize(tmp_path / "y" / f) for f in os.listdir(tmp_path / "y"))
+    assert total <= 40000 + 8 + 128 * len(got)   # the budget, the loss and the .npy headers
 
 
 def _fake_topology(root, simds):

@@ -130,15 +130,15 @@ def test_capture_after_eager_steps_continues_the_eager_run():
 
 
 def test_bench_graph_mode_prints_its_line():
-    """`bench.py --graph on` end to end at a small size (a child process: the bench owns its
-    process): one JSON line with the replay named in `launch` and the kernel timings taken from
-    the eager steps after the timed region."""
+    """`bench.py --full --graph on` end to end at a small size (a child process: the bench owns
+    its process): one JSON line with the replay named in `launch` and the kernel timings taken
+    from the eager steps after the timed region (which only --full runs)."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    p = subprocess.run([sys.executable, "bench.py", "--graph", "on", "--steps", "4", "--warmup", "2",
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--graph", "on", "--steps", "4", "--warmup", "2",
                         "--batch", "2", "--seq", "300", "--segments", "2", "--cpu-baseline", "off"],
                        cwd=root, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]

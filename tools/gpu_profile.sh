@@ -11,7 +11,7 @@ mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 if [ -z "$SKIP_BENCH" ]; then
   echo "bench"
-  timeout -k 10 500 python3 "$R/bench.py" > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
+  timeout -k 10 500 python3 "$R/bench.py" --full > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err"
 fi
 echo "kernel trace"
 timeout -k 10 500 rocprofv3 --kernel-trace --stats -f csv -d "$O/prof_$TAG" -o run -- \

@@ -22,6 +22,6 @@ python3 "$R/tools/pmc_traffic.py" $(ls "$O"/pmc_fetch_${TAG}_fp32/*/*counter_col
   $(ls "$O"/pmc_write_${TAG}_fp32/*/*counter_collection.csv "$O"/pmc_write_${TAG}_fp32/*counter_collection.csv 2>/dev/null | head -1) \
   "$O/pmc_traffic_${TAG}.json" ctc/fp32
 echo "bench fp32"
-timeout -k 10 500 python3 "$R/bench.py" --dtype fp32 > "$O/bench_${TAG}_fp32.json" 2> "$O/bench_${TAG}_fp32.err"
+timeout -k 10 500 python3 "$R/bench.py" --full --dtype fp32 > "$O/bench_${TAG}_fp32.json" 2> "$O/bench_${TAG}_fp32.err"
 cat "$O/bench_$TAG.json" "$O/bench_${TAG}_fp32.json"
 echo done
