@@ -36,6 +36,8 @@
  *   sc_rnnt_*         <- warp_rnnt `rnnt_loss(log_probs, labels, frames_lengths, labels_lengths,
  *                        blank, compact, gather=True)` called at model.py:97-105 (train.py:38-42,
  *                        :144); the log_softmax of model.py:93 optionally fused
+ *   sc_rnnt_greedy_decode <- (absent in the reference: decoder.py is CTC only) greedy decoding
+ *                        of RNNTPredictorJoiner (model.py:112-145), offline and streaming
  */
 #ifndef STATECATCHER_H
 #define STATECATCHER_H
@@ -792,6 +794,43 @@ int sc_rnnt_joint_bwd(const float* enc, const float* pred, const void* W, const 
                       const int64_t* labels_lengths, int blank, const float* scale, float* d_enc,
                       float* d_pred, float* dW, float* db, const void* workspace,
                       size_t workspace_bytes, void* stream);
+
+/*
+ * Greedy transducer decoding for the stateless predictor of RNNTPredictorJoiner
+ * (model.py:112-145: pred_proj(embedding(prev_token)) depends only on the last emitted token).
+ * The reference has no transducer decoder; this is what its CTC-only decoder.py lacks.
+ *   enc_p    [B][T][J]  joiner.enc_proj(enc_out); element strides stride_b, stride_t, inner 1
+ *   pred_tab [V][J]     joiner.pred_proj(joiner.embedding.weight): the predictor output for every
+ *                       possible previous token, contiguous
+ *   W        [V][J]     joiner.joiner.weight, contiguous;  bias fp32 [V] = joiner.joiner.bias
+ *   enc_p, pred_tab and W share `dtype` (fp32 / bf16 / f16).  All are widened to fp32 on load;
+ *   z and the dot products stay fp32 (tanh to ~1e-6 absolute).  This differs on purpose from
+ *   sc_rnnt_joint_fwd, which rounds W and z to bf16 for its MFMAs: decoding follows the
+ *   reference's fp32 arithmetic on the master weights.
+ *   lengths  int64 [B] or null: frames t >= lengths[b] are dead
+ *   mask     fp32 or null: frame (b, t) is dead where mask[b*mask_b + t*mask_t] == 0 (the meaning
+ *            of sc_ctc_greedy_frames' mask)
+ *   prev     int32 [B] or null, in/out: the last emitted token of each stream, read at entry and
+ *            written at exit, so a stream decoded in chunks equals the stream decoded whole.  Null
+ *            (or a value outside [0, V)) starts the stream at `blank`, the prefix compute_loss
+ *            feeds the predictor (model.py:77-83).
+ * Per stream b, u = prev[b], for each live frame t in order, at most max_symbols (1..64) times:
+ *   z = tanh(enc_p[b][t] + pred_tab[u]);  logit[v] = W[v] . z + bias[v];  k = argmax_v logit
+ *   (first maximal index, a NaN counting as maximal, as sc_ctc_greedy_decode);  k == blank: next
+ *   frame;  otherwise emit k at frame t, u = k, repeat.
+ *   tokens int32 [B][cap]: the emitted tokens in order;  frames int32 [B][cap] or null: the frame
+ *   index of each emission;  counts int32 [B]: the number of emissions, even beyond cap.  Nothing
+ *   is written at or beyond index cap; entries past counts[b] are left untouched.
+ * One persistent workgroup per stream.  J == 64 and V <= 1024 (W 16-byte aligned) keeps a row of W
+ * per lane in registers; any other V and J <= 256 reads W from memory at every evaluation.
+ * B == 0 and T == 0 launch nothing (T == 0 zeroes counts).  No host sync, no allocation.
+ */
+int sc_rnnt_greedy_decode(const void* enc_p, const void* pred_tab, const void* W, int dtype,
+                          const float* bias, int B, int T, int V, int J, int64_t stride_b,
+                          int64_t stride_t, const int64_t* lengths, const float* mask,
+                          int64_t mask_b, int64_t mask_t, int blank, int max_symbols,
+                          int32_t* prev, int32_t* tokens, int32_t* frames, int cap,
+                          int32_t* counts, void* stream);
 
 #ifdef __cplusplus
 }

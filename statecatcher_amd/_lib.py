@@ -131,6 +131,9 @@ _SIGS = {
                           _vp, _vp, _i32, _fp, _vp, _c.c_size_t, _vp]),
     "sc_rnnt_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i64,
                           _vp, _vp, _i32, _fp, _vp, _i32, _vp, _c.c_size_t, _vp]),
+    "sc_rnnt_greedy_decode": (_i32, [_vp, _vp, _vp, _i32, _fp, _i32, _i32, _i32, _i32, _i64, _i64,
+                                     _vp, _fp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
+                                     _vp]),
 }
 EXPORTED = tuple(_SIGS)
 

@@ -19,6 +19,7 @@
 //   gemm_tn         LinearSafe forward / input gradient GEMMs (bf16)  lucyrnn_triton.py:20-25, :107-109
 //   gemm_wgrad      LinearSafe / output_proj weight gradient           lucyrnn_triton.py:20-25, :107-109
 //   clip_adam_      clip_grad_norm_(params, max_norm) + optim.Adam/AdamW.step()  train.py:543-552
+//   rnnt_greedy_decode  (absent in the reference) greedy decode of RNNTPredictorJoiner  model.py:112-145
 // There is no CPU kernel: calling an op on CPU tensors raises (no silent fallback).
 
 #include <ATen/ATen.h>
@@ -398,6 +399,67 @@ std::tuple<Tensor, Tensor> ctc_greedy_decode_hip(const Tensor& lp_in, const Tens
 std::tuple<Tensor, Tensor> ctc_greedy_decode_meta(const Tensor& lp, const Tensor& lengths, int64_t blank) {
   auto io = lp.options().dtype(at::kInt);
   return {at::empty({lp.size(0), lp.size(1)}, io), at::empty({lp.size(0)}, io)};
+}
+
+// Greedy transducer decode of the stateless-predictor joiner (include/statecatcher.h,
+// sc_rnnt_greedy_decode).  frames is [B,cap] when return_frames, else an empty [B,0].
+std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_hip(
+    const Tensor& enc_in, const Tensor& pred_tab, const Tensor& W, const Tensor& bias,
+    const optional<Tensor>& lengths_in, const optional<Tensor>& mask, int64_t blank,
+    int64_t max_symbols, const optional<Tensor>& prev, optional<int64_t> cap_in,
+    bool return_frames) {
+  c10::DeviceGuard guard(enc_in.device());
+  const char* me = "statecatcher::rnnt_greedy_decode: ";
+  TORCH_CHECK(enc_in.dim() == 3 && pred_tab.dim() == 2 && W.dim() == 2 && bias.dim() == 1, me,
+              "enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]");
+  Tensor enc = enc_in.stride(2) == 1 || enc_in.numel() == 0 ? enc_in : enc_in.contiguous();
+  const int64_t B = enc.size(0), T = enc.size(1), J = enc.size(2), V = W.size(0);
+  TORCH_CHECK(W.size(1) == J && pred_tab.size(0) == V && pred_tab.size(1) == J && bias.numel() == V,
+              me, "pred_tab / W must be [V,J] and bias [V]");
+  TORCH_CHECK(pred_tab.scalar_type() == enc.scalar_type() && W.scalar_type() == enc.scalar_type(),
+              me, "enc_p, pred_tab and W must share one dtype");
+  Tensor pc = pred_tab.contiguous(), wc = W.contiguous(), bc = f32c(bias);
+  optional<Tensor> lens;
+  if (lengths_in && lengths_in->defined()) {
+    lens = lengths_in->to(at::kLong).contiguous();
+    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
+  }
+  int64_t mb = 0, mt = 0;
+  if (mask && mask->defined()) {
+    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
+                mask->size(1) == T, me, "mask must be fp32 [B,T]");
+    mb = mask->stride(0);
+    mt = mask->stride(1);
+  }
+  if (prev && prev->defined())
+    TORCH_CHECK(prev->scalar_type() == at::kInt && prev->numel() == B && prev->is_contiguous(), me,
+                "prev must be contiguous int32 [B]");
+  const int64_t cap = cap_in ? *cap_in : T * max_symbols;
+  TORCH_CHECK(cap >= 0 && cap <= INT32_MAX, me, "cap out of range");
+  auto io = enc.options().dtype(at::kInt);
+  Tensor tokens = at::empty({B, cap}, io), counts = at::empty({B}, io);
+  Tensor frames = at::empty({B, return_frames ? cap : 0}, io);
+  sc_check(sc_rnnt_greedy_decode(
+               enc.data_ptr(), pc.data_ptr(), wc.data_ptr(), dtype_code(enc),
+               (const float*)bc.data_ptr(), (int)B, (int)T, (int)V, (int)J, enc.stride(0),
+               enc.stride(1), (const int64_t*)opt_ptr(lens), (const float*)opt_ptr(mask), mb, mt,
+               (int)blank, (int)max_symbols, (int32_t*)opt_ptr(prev), (int32_t*)tokens.data_ptr(),
+               return_frames ? (int32_t*)frames.data_ptr() : nullptr, (int)cap,
+               (int32_t*)counts.data_ptr(), stream_for(enc)),
+           "statecatcher::rnnt_greedy_decode");
+  return {tokens, counts, frames};
+}
+
+std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_meta(
+    const Tensor& enc, const Tensor& pred_tab, const Tensor& W, const Tensor& bias,
+    const optional<Tensor>& lengths, const optional<Tensor>& mask, int64_t blank,
+    int64_t max_symbols, const optional<Tensor>& prev, optional<int64_t> cap_in,
+    bool return_frames) {
+  TORCH_CHECK(enc.dim() == 3 && W.dim() == 2 && W.size(1) == enc.size(2),
+              "statecatcher::rnnt_greedy_decode: enc_p [B,T,J], W [V,J]");
+  const int64_t B = enc.size(0), cap = cap_in ? *cap_in : enc.size(1) * max_symbols;
+  auto io = enc.options().dtype(at::kInt);
+  return {at::empty({B, cap}, io), at::empty({B}, io), at::empty({B, return_frames ? cap : 0}, io)};
 }
 
 // ------------------------------------------------------------------------------ mLSTM --------
@@ -801,6 +863,10 @@ TORCH_LIBRARY(statecatcher, m) {
   m.def("rnnt_joint_bwd(Tensor enc_p, Tensor pred_p, Tensor W, Tensor bias, Tensor labels, "
         "Tensor frames_lengths, Tensor labels_lengths, Tensor workspace, Tensor scale, int blank=0)"
         " -> (Tensor d_enc, Tensor d_pred, Tensor dW, Tensor dbias)");
+  m.def("rnnt_greedy_decode(Tensor enc_p, Tensor pred_tab, Tensor W, Tensor bias, "
+        "Tensor? lengths=None, Tensor? mask=None, int blank=0, int max_symbols=4, "
+        "Tensor(a!)? prev=None, int? cap=None, bool return_frames=False)"
+        " -> (Tensor tokens, Tensor counts, Tensor frames)");
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
@@ -822,6 +888,7 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("gemm_tn", &gemm_tn_hip);
   m.impl("gemm_wgrad", &gemm_wgrad_hip);
   m.impl("clip_adam_", &clip_adam_hip);
+  m.impl("rnnt_greedy_decode", &rnnt_greedy_decode_hip);
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
@@ -843,4 +910,5 @@ TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("gemm_tn", &gemm_tn_meta);
   m.impl("gemm_wgrad", &gemm_wgrad_meta);
   m.impl("clip_adam_", &clip_adam_meta);
+  m.impl("rnnt_greedy_decode", &rnnt_greedy_decode_meta);
 }

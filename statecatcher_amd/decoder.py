@@ -1,7 +1,8 @@
-"""Drop-in of /root/reference/decoder.py:3-30 running on the GPU (one host copy, no per-frame sync)."""
+"""Drop-in of /root/reference/decoder.py:3-30 running on the GPU (one host copy, no per-frame sync),
+and the transducer counterpart the reference does not have."""
 import torch
 
-from .ops import ctc_greedy_decode
+from .ops import ctc_greedy_decode, rnnt_greedy_decode
 
 
 def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
@@ -10,3 +11,39 @@ def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
     tokens = tokens.cpu()
     counts = counts.cpu().tolist()
     return [tokens[b, :c].tolist() for b, c in enumerate(counts)]
+
+
+def rnnt_joiner_tables(joiner, dtype=None):
+    """(pred_tab [V,J], W [V,J], bias fp32 [V]) of an RNNTPredictorJoiner /
+    RNNTCompactPredictorJoiner for ops.rnnt_greedy_decode: the stateless predictor's output for
+    every possible previous token, and the output projection.  dtype: of pred_tab and W (default:
+    the joiner's own)."""
+    jm = getattr(joiner, "module", joiner)   # DDP-wrapped or not
+    with torch.no_grad():
+        pred_tab = jm.pred_proj(jm.embedding.weight)
+        W = jm.joiner.weight.detach()
+        dtype = dtype or W.dtype
+        return (pred_tab.to(dtype).contiguous(), W.to(dtype).contiguous(),
+                jm.joiner.bias.detach().float().contiguous())
+
+
+def rnnt_greedy_decoder(enc_out, joiner, input_lengths, blank=0, max_symbols=4, return_frames=False):
+    """Greedy transducer decode of encoder output enc_out [B,T,D] with ``joiner`` (either joiner
+    class of model.py) -> List[List[int]], plus the frame index of every token when asked.
+    Streams start at ``blank`` as compute_loss's predictor prefix does; at most max_symbols tokens
+    per frame.  enc_proj and the [V,J] predictor table are computed once per call, the decode is
+    one launch (ops.rnnt_greedy_decode, fp32 arithmetic) and there is one host copy at the end."""
+    jm = getattr(joiner, "module", joiner)
+    with torch.no_grad():
+        enc_p = jm.enc_proj(enc_out)
+        pred_tab, W, bias = rnnt_joiner_tables(jm, enc_p.dtype)
+        out = rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=input_lengths, blank=blank,
+                                 max_symbols=max_symbols, return_frames=return_frames)
+    n = len(out)
+    packed = torch.cat([out[1].unsqueeze(1)] + [t for i, t in enumerate(out) if i != 1], 1).cpu()
+    counts = packed[:, 0].tolist()
+    cap = out[0].shape[1]
+    toks = [packed[b, 1:1 + c].tolist() for b, c in enumerate(counts)]
+    if n == 2:
+        return toks
+    return toks, [packed[b, 1 + cap:1 + cap + c].tolist() for b, c in enumerate(counts)]

@@ -1324,6 +1324,73 @@ def ctc_greedy_frames(logits, prev, emit, mask=None, blank=0):
     check(rc, "sc_ctc_greedy_frames")
 
 
+def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, max_symbols=4,
+                       prev=None, cap=None, return_frames=False, out=None):
+    """Greedy transducer decode of a stateless-predictor joiner in one launch
+    (sc_rnnt_greedy_decode, csrc/rnnt_decode.hip): enc_p [B,T,J] = joiner.enc_proj(enc_out)
+    (unit inner stride, any other strides), pred_tab [V,J] = joiner.pred_proj(joiner.embedding.
+    weight), W [V,J] / bias [V] = joiner.joiner's; enc_p, pred_tab and W share one dtype (fp32,
+    bf16, f16), all arithmetic is fp32.  lengths int64 [B] (tensor or list) and mask fp32 [B,T]
+    (0 = dead frame) are optional; prev int32 [B] (contiguous) is the last emitted token of each
+    stream, read at entry and written at exit (None: every stream starts at ``blank``).
+
+    Returns device tensors (tokens int32 [B,cap], counts int32 [B][, frames int32 [B,cap]]):
+    the first min(counts[b], cap) entries of row b are valid, counts reports every emission;
+    cap defaults to T * max_symbols, which cannot overflow.  out = (tokens, counts, frames or
+    None): write into these instead of allocating (no allocation then: safe inside a hipGraph
+    capture).  No host sync (a ``lengths`` list is copied to the device asynchronously)."""
+    require_device(enc_p, pred_tab, W, bias, prev, mask)
+    if enc_p.dim() != 3 or pred_tab.dim() != 2 or W.dim() != 2 or bias.dim() != 1:
+        raise ValueError("rnnt_greedy_decode: enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]")
+    B, T, J = enc_p.shape
+    V = W.shape[0]
+    if tuple(W.shape) != (V, J) or tuple(pred_tab.shape) != (V, J) or bias.numel() != V:
+        raise ValueError(f"rnnt_greedy_decode: pred_tab / W must be [V,J]=[{V},{J}] and bias [V], "
+                         f"got {tuple(pred_tab.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}")
+    if pred_tab.dtype != enc_p.dtype or W.dtype != enc_p.dtype:
+        raise ValueError("rnnt_greedy_decode: enc_p, pred_tab and W must share one dtype")
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError("rnnt_greedy_decode: bias must be contiguous fp32 [V]")
+    if (T > 0 and B > 0 and enc_p.stride(2) != 1) or not pred_tab.is_contiguous() \
+            or not W.is_contiguous():
+        raise ValueError("rnnt_greedy_decode: enc_p needs unit inner stride, pred_tab / W contiguous")
+    if prev is not None and (prev.dtype != torch.int32 or prev.numel() != B
+                             or not prev.is_contiguous()):
+        raise ValueError("rnnt_greedy_decode: prev must be contiguous int32 [B]")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
+        raise ValueError("rnnt_greedy_decode: mask must be fp32 [B, T]")
+    lens = None if lengths is None else _as_len_tensor(lengths, enc_p.device)
+    if lens is not None and lens.numel() != B:
+        raise ValueError("rnnt_greedy_decode: lengths must have B entries")
+    if out is not None:
+        tokens, counts, frames = out
+        cap = tokens.shape[1]
+        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.shape[0] == B \
+            and counts.dtype == torch.int32 and counts.is_contiguous() and counts.numel() == B \
+            and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous()
+                                    and frames.shape == tokens.shape))
+        if not ok:
+            raise ValueError("rnnt_greedy_decode: out = (tokens int32 [B,cap], counts int32 [B], "
+                             "frames int32 [B,cap] or None), contiguous")
+        require_device(tokens, counts, frames)
+    else:
+        cap = T * int(max_symbols) if cap is None else int(cap)
+        if cap < 0:
+            raise ValueError(f"rnnt_greedy_decode: cap={cap} is negative")
+        tokens = torch.empty(B, cap, dtype=torch.int32, device=enc_p.device)
+        counts = torch.empty(B, dtype=torch.int32, device=enc_p.device)
+        frames = torch.empty(B, cap, dtype=torch.int32, device=enc_p.device) \
+            if return_frames else None
+    rc = _lib.load().sc_rnnt_greedy_decode(
+        ptr(enc_p), ptr(pred_tab), ptr(W), dtype_code(enc_p), ptr(bias), B, T, V, J,
+        enc_p.stride(0), enc_p.stride(1), ptr(lens), ptr(mask),
+        mask.stride(0) if mask is not None else 0, mask.stride(1) if mask is not None else 0,
+        int(blank), int(max_symbols), ptr(prev), ptr(tokens), ptr(frames), cap, ptr(counts),
+        stream_of(enc_p))
+    check(rc, "sc_rnnt_greedy_decode")
+    return (tokens, counts, frames) if return_frames else (tokens, counts)
+
+
 # ------------------------------------------------------------------- feature frontend --------
 def fbank(audio, kind="mfcc", sample_rate=16000):
     """make_frontend(kind)(audio).transpose(-1, -2) on the GPU (fbank.hip): audio fp32

@@ -37,6 +37,12 @@ The decode is incremental: ``prev`` holds each stream's last argmax (-1 at strea
 decoder.py's ``prev_token = None``), and emit[b, t] is the token decoder.py would append at
 frame t, or -1.  Frames with mask 0 (past a stream's end) keep state (lucyrnn.py:66-68) and
 emit nothing.
+
+With ``joiner`` (an RNNTPredictorJoiner / RNNTCompactPredictorJoiner) the block ends in a greedy
+transducer decode instead (the reference has none): enc_p = joiner.enc_proj(logits) over the
+block's K frames (lucy_frame_gemm on the frame engine, addmm on the library engine), then ONE
+sc_rnnt_greedy_decode launch (csrc/rnnt_decode.hip) with each stream's last emitted token carried
+in ``prev`` (``blank`` at stream start, compute_loss's predictor prefix), inside the same graph.
 """
 import torch
 
@@ -55,11 +61,15 @@ class StreamingLucyRNN:
 
     dtype: activation/weight dtype of the GEMMs (fp32 = the reference's arithmetic; bf16 for
     throughput); state is fp32 either way.  graph: capture the block as a hipGraph.
+    joiner: decode as a transducer with this joiner (at most ``max_symbols`` tokens per frame)
+    instead of greedy CTC; its weights are snapshotted too.
     """
+
+    joiner = False   # True on an instance built with a joiner: the block ends in the transducer decode
 
     def __init__(self, model: LucyRNN, batch: int, frames_per_call: int = 1,
                  dtype=torch.float32, blank: int = 0, graph: bool = True, engine: str = "auto",
-                 schedule: str = "wavefront"):
+                 schedule: str = "wavefront", joiner=None, max_symbols: int = 4):
         cfg = model.config
         dev = next(model.parameters()).device
         ops._lib.require_device(next(model.parameters()))
@@ -99,6 +109,9 @@ class StreamingLucyRNN:
             raise ValueError("schedule must be 'wavefront' or 'frame'")
         # wavefront: the frame engine's block as stages over (frame, layer) (_block_wavefront)
         self.schedule = schedule if engine == "frame" else "frame"
+        self.joiner = joiner is not None
+        if self.joiner:
+            self._init_joiner(joiner, max_symbols, dev)
         z = lambda *s, dt=dtype: torch.zeros(*s, dtype=dt, device=dev)   # noqa: E731
         if engine == "frame":
             f32 = torch.float32
@@ -130,6 +143,8 @@ class StreamingLucyRNN:
             self.logits = z(K, B, self.V, dt=f32)
             self.emit = torch.full((K, B), -1, dtype=torch.int32, device=dev)
             self.prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            if self.joiner:
+                self.enc_p = z(K, B, self.J, dt=f32)
             self.graph = None
             if graph:
                 self._capture()
@@ -146,10 +161,50 @@ class StreamingLucyRNN:
         self.logits = z(K, B, self.V)
         self.emit = torch.full((K, B), -1, dtype=torch.int32, device=dev)
         self.prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        if self.joiner:
+            self.enc_p = z(K, B, self.J)
         self.graph = None
         if graph:
             self._capture()
         self.reset()
+
+    def _init_joiner(self, joiner, max_symbols, dev):
+        """Snapshot the joiner: enc_proj for the block's projection, the [V, J] predictor table
+        and the output projection for the decode (fp32 on the frame engine, whose activations
+        are fp32; ``dtype`` on the library engine), and the static decode outputs."""
+        from .decoder import rnnt_joiner_tables
+        jm = getattr(joiner, "module", joiner)
+        B, K, V = self.B, self.K, self.V
+        if jm.enc_proj.in_features != V or jm.joiner.out_features != V:
+            raise ValueError(f"joiner must project the model's {V} outputs and emit {V} tokens")
+        if not 1 <= int(max_symbols) <= 64:
+            raise ValueError("max_symbols must be in [1, 64]")
+        self.max_symbols, self.J = int(max_symbols), jm.enc_proj.out_features
+        frame = self.engine == "frame"
+        if frame and (V % 8 != 0 or V > 2048):
+            raise ValueError("engine='frame' with a joiner needs vocab_size % 8 == 0 and <= 2048 "
+                             "(enc_proj runs on lucy_frame_gemm); use engine='library'")
+        wdt = self.dtype
+        self.w_enc = jm.enc_proj.weight.detach().to(wdt).contiguous()
+        self.b_enc = jm.enc_proj.bias.detach().to(torch.float32 if frame else wdt).contiguous()
+        self.pred_tab, self.w_join, self.b_join = rnnt_joiner_tables(
+            jm, torch.float32 if frame else wdt)
+        cap = K * self.max_symbols
+        self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+        self.tok_frames = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _rnnt_block(self):
+        """enc_proj over the block's K frames of logits, then one greedy transducer launch."""
+        K, B = self.K, self.B
+        lg, ep = self.logits.view(K * B, self.V), self.enc_p.view(K * B, self.J)
+        if self.engine == "frame":
+            ops.lucy_frame_gemm(ops.FRAME_PLAIN, lg, self.w_enc, self.b_enc, ep)
+        else:
+            torch.addmm(self.b_enc, lg, self.w_enc.t(), out=ep)
+        ops.rnnt_greedy_decode(self.enc_p.transpose(0, 1), self.pred_tab, self.w_join, self.b_join,
+                               mask=self.mask.t(), blank=self.blank, max_symbols=self.max_symbols,
+                               prev=self.prev, out=(self.tokens, self.counts, self.tok_frames))
 
     # ------------------------------------------------------------------------------ frame --
     def _frame_fused_chain(self, j):
@@ -178,7 +233,8 @@ class StreamingLucyRNN:
                                  st_h=st_h, lnz=e["lnz"], lnh=e["lnh"], mask=m)
             inp = self.xo[l]
         ops.lucy_frame_gemm(ops.FRAME_PLAIN, inp, self.w_out, self.b_out, self.logits[j])
-        ops.ctc_greedy_step(self.logits[j], self.prev, self.emit[j], mask=m, blank=self.blank)
+        if not self.joiner:
+            ops.ctc_greedy_step(self.logits[j], self.prev, self.emit[j], mask=m, blank=self.blank)
 
     def _frame(self, j):
         if self.engine == "frame":
@@ -203,7 +259,8 @@ class StreamingLucyRNN:
                                    e["lnz"], e["lnh"], hp=self.hp, mask=m)
             inp = self.xo[l]
         torch.addmm(self.b_out, inp, self.w_out.t(), out=self.logits[j])
-        ops.ctc_greedy_step(self.logits[j], self.prev, self.emit[j], mask=m, blank=self.blank)
+        if not self.joiner:
+            ops.ctc_greedy_step(self.logits[j], self.prev, self.emit[j], mask=m, blank=self.blank)
 
     def _block_wavefront(self):
         """The frame engine's block as K + L - 1 stages: stage tau runs layer l of frame tau - l
@@ -255,6 +312,8 @@ class StreamingLucyRNN:
             ops.lucy_frame_cellb_multi(cells, stream)
         ops.lucy_frame_gemm(ops.FRAME_PLAIN, self.xlast.view(K * self.B, D), self.w_out, self.b_out,
                             self.logits.view(K * self.B, self.V))
+        if self.joiner:
+            return self._rnnt_block()
         ops.ctc_greedy_frames(self.logits, self.prev, self.emit, mask=self.mask, blank=self.blank)
 
     def _block(self):
@@ -262,6 +321,8 @@ class StreamingLucyRNN:
             return self._block_wavefront()
         for j in range(self.K):
             self._frame(j)
+        if self.joiner:
+            self._rnnt_block()
 
     def _capture(self):
         side = torch.cuda.Stream(self.x.device)
@@ -276,8 +337,8 @@ class StreamingLucyRNN:
     # ------------------------------------------------------------------------------- API ---
     def reset(self, hidden_states=None, streams=None):
         """Start streams afresh: state from ``hidden_states`` ((h list, s list) of [B,D], as the
-        reference's forward takes) or zero, prev token = none.  ``streams``: index tensor/list
-        of the streams to reset (default all)."""
+        reference's forward takes) or zero, prev token = none (``blank`` with a joiner).
+        ``streams``: index tensor/list of the streams to reset (default all)."""
         idx = slice(None) if streams is None else torch.as_tensor(streams, device=self.x.device)
         for l in range(self.L):
             for buf, src in ((self.h[l], None if hidden_states is None else hidden_states[0][l]),
@@ -286,7 +347,7 @@ class StreamingLucyRNN:
                     buf[idx] = 0.0
                 else:
                     buf[idx] = src.to(buf.device, torch.float32)[idx]
-        self.prev[idx] = -1
+        self.prev[idx] = self.blank if self.joiner else -1
 
     def state(self):
         """(h list, s list) fp32 copies — the reference's (h, s) return (lucyrnn.py:188-189)."""
@@ -296,7 +357,10 @@ class StreamingLucyRNN:
         """Advance every stream by K = frames_per_call model frames.  x [B, K, input_dim *
         stack_order] (already stacked); mask [B, K] (bool/float, None = all live).  Returns
         emit int32 [B, K] on the device: the token decoder.py appends at that frame, or -1.
-        The logits of the block stay in ``self.logits`` ([K, B, V])."""
+        The logits of the block stay in ``self.logits`` ([K, B, V]).
+        With a joiner: returns (tokens int32 [B, K * max_symbols], frames, counts int32 [B]) on
+        the device instead: row b's first counts[b] tokens are this block's emissions, frames
+        their frame index within the block; later entries are stale."""
         self.x.copy_(x.transpose(0, 1))
         if mask is None:
             self.mask.fill_(1.0)
@@ -306,6 +370,8 @@ class StreamingLucyRNN:
             self.graph.replay()
         else:
             self._block()
+        if self.joiner:
+            return self.tokens, self.tok_frames, self.counts
         return self.emit.t()
 
     def decode(self, feats, masks=None, return_logits=False):
@@ -328,11 +394,20 @@ class StreamingLucyRNN:
             xb[:, :n] = x[:, t0:t0 + n]
             mb = torch.zeros(B, self.K, device=self.x.device)   # padding frames are masked out
             mb[:, :n] = 1.0 if m is None else m[:, t0:t0 + n]
-            emits.append(self.step(xb, mb)[:, :n].clone())
+            if self.joiner:
+                tk, _, ct = self.step(xb, mb)
+                emits.append(torch.cat([ct.unsqueeze(1), tk], 1))   # (a copy: count, tokens)
+            else:
+                emits.append(self.step(xb, mb)[:, :n].clone())
             if return_logits:
                 logits.append(self.logits[:n].transpose(0, 1).clone())
         em = torch.cat(emits, 1).cpu() if emits else torch.zeros(B, 0, dtype=torch.int32)
-        toks = [[int(t) for t in row if t >= 0] for row in em]
+        if self.joiner:
+            w = 1 + self.K * self.max_symbols
+            toks = [[t for k in range(0, em.shape[1], w) for t in row[k + 1:k + 1 + row[k]]]
+                    for row in em.tolist()]
+        else:
+            toks = [[int(t) for t in row if t >= 0] for row in em]
         if return_logits:
             return toks, torch.cat(logits, 1) if logits else None
         return toks

@@ -20,6 +20,7 @@ Reference interfaces (what a ``train.py`` user swaps in):
   gemm_tn     <- LinearSafe's forward / input-gradient GEMM (bf16)    lucyrnn_triton.py:20-25
   gemm_wgrad  <- LinearSafe / output_proj weight gradient             lucyrnn_triton.py:20-25, :107-109
   clip_adam_  <- clip_grad_norm_(params, 50) + optim.Adam/AdamW.step() train.py:543-552
+  rnnt_greedy_decode <- (absent in the reference) greedy decode of RNNTPredictorJoiner, model.py:112-145
 """
 import os
 
@@ -29,7 +30,7 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_torch_ops.
 OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay_scan_bwd",
        "layer_norm_fwd", "layer_norm_bwd", "ctc_fwd", "ctc_bwd", "ctc_mean", "ctc_greedy_decode",
        "mlstm_fwd", "mlstm_bwd", "mlstm_gate_bwd", "rnnt_joint_fwd", "rnnt_joint_bwd",
-       "gemm_tn", "gemm_wgrad", "clip_adam_")
+       "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode")
 
 _LOADED = False
 
@@ -232,6 +233,15 @@ def rnnt_joint_nll(enc_p, pred_p, W, bias, labels, frames_lengths, labels_length
     warp_rnnt's gathered lattice) without materialising the (B, T, U+1, V) logits."""
     return load().rnnt_joint_fwd(enc_p, pred_p, W, bias, labels, frames_lengths, labels_lengths,
                                  blank)[0]
+
+
+def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, max_symbols=4,
+                       prev=None, cap=None, return_frames=False):
+    """(tokens int32 [B,cap], counts int32 [B][, frames int32 [B,cap]]) of the greedy transducer
+    decode (ops.rnnt_greedy_decode); prev int32 [B] is updated in place when given."""
+    tokens, counts, frames = load().rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths, mask,
+                                                       blank, max_symbols, prev, cap, return_frames)
+    return (tokens, counts, frames) if return_frames else (tokens, counts)
 
 
 def gemm_tn(a, b, tile_m=0):
