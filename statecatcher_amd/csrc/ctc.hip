@@ -45,34 +45,10 @@
 //                     log-sums, then one coalesced 16-byte pass writing the gradient row
 #include "sc_common.h"
 
-#ifndef SC_CTC_ABL   // ablation bitmask (timing studies only; results are wrong when set):
-#define SC_CTC_ABL 0  // 1 no halo exchange, 2 no per-step stores, 4 max instead of log-sum-exp,
-#endif                // (ctc_lin_kernel) 8 no renormalisation, 16 no emission loads
-#ifndef SC_CTC_KMAX   // most steps between halo exchanges (8 or 16)
-#define SC_CTC_KMAX 16
-#endif
-// SC_CTC_FLAGX: the halo exchanges that do not re-centre hand the halo to the one neighbour that
-// reads it through an LDS flag (the writer's exchange count) instead of a workgroup barrier; the
-// re-centring exchanges keep the barrier (they need the workgroup maximum).  0: every exchange
-// on the barrier (A/B only).
-// Measured (tools/r5_ctc.sh, scan_bench ctc_fwd at C2 size, alternated): flags 233.6 us vs
-// barriers 211.6 us -- the chained waits (wave w on w - 1 on w - 2 ...) cost more than the
-// barrier they replace, so the barrier stays.
-#ifndef SC_CTC_FLAGX
-#define SC_CTC_FLAGX 0
-#endif
-// SC_CTC_WMV: 1 = the re-centring exchange reads the wave maxima as float4s.  Measured slower
-// (tools/r5_pc.sh, scan_bench ctc_fwd: 211.4-212.0 us vs 199.9-200.0 us for the scalar loop)
-#ifndef SC_CTC_WMV
-#define SC_CTC_WMV 0
-#endif
-#ifndef SC_CTC_FLAG_SLEEP   // (SC_CTC_FLAGX) s_sleep in the flag spin
-#define SC_CTC_FLAG_SLEEP 1
-#endif
-
 namespace sc {
 
 constexpr float kNegInf = -__builtin_huge_valf();
+constexpr int kCtcKmax = 16;   // most steps between halo exchanges
 
 struct CtcWs {
   float* lse;     // [B,T]      natural-log row normaliser (logits input)
@@ -327,35 +303,16 @@ __global__ void __launch_bounds__(256) ctc_chain_kernel(CtcArgs a) {
 }
 
 // ---------------------------------------------------------------------------- alpha / beta --
-__device__ __forceinline__ float shr1(float v) {   // value of lane-1 (lane 0: dead)
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-1e30f), __float_as_int(v),
-                                                     0x138, 0xf, 0xf, false));
-}
-__device__ __forceinline__ float shl1(float v) {   // value of lane+1 (lane 63: dead)
-  return __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(-1e30f), __float_as_int(v),
-                                                     0x130, 0xf, 0xf, false));
-}
-
 // Branch-free log2-sum-exp for the lattice: "dead" states carry kDead (finite), so no -inf
 // test is needed; exp2 of anything ~kDead below the max is exactly 0.
 constexpr float kDead = -1e30f;
 // a re-centring that finds the lattice's maximum this many bits below the last one sends the
 // sequence to the exact lattice (ctc_x64_kernel): |values| ~ 512 round by ~3e-5 per step
 constexpr float kDrift = 512.0f;
-__device__ __forceinline__ float lse3_live(float a, float b, float c) {
-  const float m = fmaxf(fmaxf(a, b), c);
-  if (SC_CTC_ABL & 4) return m;
-  // the max term is exp2(0) = 1: two exponentials (median and minimum), not three
-  const float md = __builtin_amdgcn_fmed3f(a, b, c);
-  const float lo = fminf(fminf(a, b), c);
-  return m + log2_(1.0f + exp2_(md - m) + exp2_(lo - m));
-}
 
 constexpr int kAbP = 16;   // emission prefetch depth (steps)
 
-#ifndef SC_CTC_V2   // 1: lattice step without canonicalising max/min, emission selects or a swap
-#define SC_CTC_V2 1
-#endif
+// The lattice step runs without canonicalising max/min, emission selects or a swap:
 // max / min / max3 / min3 as single instructions: fmaxf & co. make LLVM canonicalise loop-carried
 // operands first (one extra v_max per value per step); the lattice never holds NaN it must quiet
 __device__ __forceinline__ float vmin(float a, float b) {
@@ -398,7 +355,6 @@ __device__ __forceinline__ f2v lse23(float a2, float b2, float a3, float b3, flo
 
 __device__ __forceinline__ float lse2_live(float a, float b) {
   const float m = fmaxf(a, b);
-  if (SC_CTC_ABL & 4) return m;
   return m + log2_(1.0f + exp2_(fminf(a, b) - m));
 }
 
@@ -437,15 +393,8 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
   }
   extern __shared__ __attribute__((aligned(16))) float2 full2[];   // [2][nw*OW] published pairs
   __shared__ __attribute__((aligned(16))) float wmax[16];
-  __shared__ int xflag[16];   // (SC_CTC_FLAGX) exchanges published by each wave
-  if (SC_CTC_FLAGX) {
-    if (tid < 16) xflag[tid] = 0;
-    lds_barrier();
-  }
   const int nst = nw * OW;
   const int pc = p < 0 ? 0 : (2 * p >= a.Sp ? a.Sp / 2 - 1 : p);   // clamped for addressing only
-  const float2* lrow = (const float2*)(a.ws.lpe + (int64_t)b * a.T * a.Sp) + pc;
-  const int64_t rs = a.Sp / 2;   // row stride in pairs
   // Per-step outputs through buffer descriptors: lanes that must not write (halo lanes, pairs
   // past the row; every lane but 0 for the offset) get an out-of-range offset, which the buffer
   // unit drops, so the stores need no exec-mask branch in the step loop.
@@ -459,7 +408,6 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
   if (tid == 0) offn[0] = 0.0;
   auto tstep = [&](int i) { return BETA ? Tb - 1 - i : i; };
   float2 bufA[kAbP], bufB[kAbP];
-#if SC_CTC_V2
   // emission pairs through a buffer descriptor: lanes outside the row (alpha's leading halo,
   // pairs past Sp) get an out-of-range offset and read 0, which keeps a dead state dead (its
   // inputs are all dead); live lanes past 2 Ub + 1 read the -1e30 padding ctc_emit wrote
@@ -472,12 +420,6 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
       buf[j] = __builtin_bit_cast(float2, __builtin_amdgcn_raw_buffer_load_b64(
                                               ers, evo, (uint32_t)tstep(min(i0 + j, Tb - 1)) * rowb, 0));
   };
-#else
-  auto load = [&](float2 (&buf)[kAbP], int i0) {
-#pragma unroll
-    for (int j = 0; j < kAbP; ++j) buf[j] = lrow[(int64_t)tstep(min(i0 + j, Tb - 1)) * rs];
-  };
-#endif
   auto emit = [&](int t, float vB, float vL) {
     __builtin_amdgcn_raw_buffer_store_b64(
         __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, make_float2(vB, vL)), ors,
@@ -491,7 +433,6 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
     for (int j = 0; j < kAbP; ++j) {
       const int i = i0 + j;
       if (i >= Tb) break;
-#if SC_CTC_V2
       if (i == 0) {
         vB = (liveB && p == (BETA ? Ub : 0)) ? buf[j].x : kDead;
         vL = (liveL && p == (BETA ? Ub - 1 : 0)) ? buf[j].y : kDead;
@@ -507,61 +448,15 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
         vB = r.x;
         vL = r.y;
       }
-#else
-      const float eB = liveB ? buf[j].x : kDead;
-      const float eL = liveL ? buf[j].y : kDead;
-      if (i == 0) {
-        vB = (liveB && p == (BETA ? Ub : 0)) ? eB : kDead;
-        vL = (liveL && p == (BETA ? Ub - 1 : 0)) ? eL : kDead;
-      } else if (!BETA) {
-        const float lp = shr1(vL);
-        const float nB = lse2_live(vB, lp) + eB;
-        vL = lse3_live(vL, vB, skip ? lp : kDead) + eL;
-        vB = nB;
-      } else {
-        const float bn = shl1(vB);
-        const float ln = shl1(vL);
-        const float nB = lse2_live(vB, vL) + eB;
-        vL = lse3_live(vL, bn, skip ? ln : kDead) + eL;
-        vB = nB;
-      }
-#endif
-      if (!(SC_CTC_ABL & 1) && j % K == K - 1) {   // halo exchange (+ re-centre every 2nd)
+      if (j % K == K - 1) {   // halo exchange (+ re-centre every 2nd)
         const int par = exch & 1;
         const bool norm = par == 1;
         if (own) full2[par * nst + p] = make_float2(vB, vL);
         // (buffer 0 is written only at the exchanges that do not re-centre: the barrier of the
         // re-centring exchange between two of them orders every read before the next write)
-        if (SC_CTC_FLAGX && !norm) {
-          // the halo comes from one neighbour (alpha: wave w - 1, beta: w + 1): publish this
-          // wave's count after its pairs (one wave's LDS operations complete in order), then wait
-          // for the neighbour's
-          lds_read_wait();   // (every lane's pairs written before lane 0's count)
-          if (lane == 0)
-            __hip_atomic_store(&xflag[w], exch + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-          const int nb = BETA ? w + 1 : w - 1;
-          if (nb >= 0 && nb < nw) {
-            while (__hip_atomic_load(&xflag[nb], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <= exch)
-              if (SC_CTC_FLAG_SLEEP) __builtin_amdgcn_s_sleep(1);
-          }
-          if (!own) {
-            const bool has = p >= 0 && p < nst;
-            const float2 q = has ? full2[par * nst + p] : make_float2(kDead, kDead);
-            vB = q.x;
-            vL = q.y;
-          }
-          ++exch;
-          if (!(SC_CTC_ABL & 2)) emit(tstep(i), vB, vL);
-          continue;
-        }
         if (norm) {
           float m = own ? fmaxf(vB, vL) : kDead;
-#if SC_CTC_V2
           m = wave_max_dpp(m);
-#else
-#pragma unroll
-          for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-#endif
           if (lane == 0) wmax[w] = m;
         }
         lds_barrier();
@@ -573,20 +468,7 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
         }
         if (norm) {
           float m = kDead;
-#if SC_CTC_WMV
-#pragma unroll
-          for (int q4 = 0; q4 < 16; q4 += 4) {   // (nw <= 16: four 16-byte reads, unused slots skipped)
-            if (q4 < nw) {
-              const float4 wm = *(const float4*)&wmax[q4];
-              m = fmaxf(m, q4 + 0 < nw ? wm.x : kDead);
-              m = fmaxf(m, q4 + 1 < nw ? wm.y : kDead);
-              m = fmaxf(m, q4 + 2 < nw ? wm.z : kDead);
-              m = fmaxf(m, q4 + 3 < nw ? wm.w : kDead);
-            }
-          }
-#else
           for (int q = 0; q < nw; ++q) m = fmaxf(m, wmax[q]);
-#endif
           if (m > 0.5f * kDead) {   // all dead (infeasible): keep the sentinel
             vB -= m;
             vL -= m;
@@ -599,7 +481,7 @@ __device__ __forceinline__ void ab_run(const CtcArgs& a, int b, int Tb, int Ub) 
         }
         ++exch;
       }
-      if (!(SC_CTC_ABL & 2)) emit(tstep(i), vB, vL);
+      emit(tstep(i), vB, vL);
     }
   };
   load(bufA, 0);
@@ -751,8 +633,7 @@ __device__ __forceinline__ bool lin_produce(const CtcArgs& a, int b, int Tb, int
       const uint32_t so = (uint32_t)tstep(min(i0 + s, Tb - 1)) * rowb;
 #pragma unroll
       for (int j = 0; j < PPL; ++j)
-        buf[s][j] = (SC_CTC_ABL & 16) ? f2v{0.5f, 0.25f}
-                                      : __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(ers, vo[j], so, 0));
+        buf[s][j] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(ers, vo[j], so, 0));
     }
   };
   double vB[PPL], vL[PPL];
@@ -803,7 +684,7 @@ __device__ __forceinline__ bool lin_produce(const CtcArgs& a, int b, int Tb, int
           vL[j] = nl;
         }
       }
-      if (!(SC_CTC_ABL & 8) && (i + 1) % kAb1R == 0) {   // renormalise the wave max to [0.5, 1)
+      if ((i + 1) % kAb1R == 0) {   // renormalise the wave max to [0.5, 1)
         double m = 0.0;
 #pragma unroll
         for (int j = 0; j < PPL; ++j) m = fmax(m, fmax(vB[j], vL[j]));
@@ -899,10 +780,9 @@ __device__ __forceinline__ void lin_consume(const CtcArgs& a, int b, int Tb, con
 #pragma unroll
       for (int j = 0; j < PPL; ++j) {
         const d2v v = slot[(s * PPL + j) * 64 + lane];
-        if (!(SC_CTC_ABL & 2))
-          __builtin_amdgcn_raw_buffer_store_b64(
-              __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, f2v{log2d(v.x), log2d(v.y)}),
-              ors, vo[j], so, 0);
+        __builtin_amdgcn_raw_buffer_store_b64(
+            __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, f2v{log2d(v.x), log2d(v.y)}),
+            ors, vo[j], so, 0);
       }
     }
   };
@@ -1199,11 +1079,11 @@ static int x64_ppl(int Umax) {
 }
 
 // pairs per lane of the one-wave lattice family (0: the multi-wave kernel).  Off unless
-// SC_CTC_LIN=1 in the environment.  Measured at C2 (tools/scan_bench.py --only ctc, ablation
-// builds of tools/ctc_abl.sh; profiles/r4_lattice_ab.md): emit + chain + lattice 256 us against
-// 211 us for the multi-wave log-space kernel, and the gradient 60 us slower on the fp64 rows.
-// Dropping the per-step stores (ABL 2) takes 62 us off: vmcnt retires loads and stores in issue
-// order, so waiting for a prefetched emission row also waits for the older row stores.
+// SC_CTC_LIN=1 in the environment.  Measured at C2 (tools/scan_bench.py --only ctc;
+// profiles/r4_lattice_ab.md): emit + chain + lattice 256 us against 211 us for the multi-wave
+// log-space kernel, and the gradient 60 us slower on the fp64 rows.  An ablation build without
+// the per-step stores ran 62 us faster: vmcnt retires loads and stores in issue order, so
+// waiting for a prefetched emission row also waits for the older row stores.
 static int lin_ppl(int Umax) {
   static const bool on = [] {
     const char* e = getenv("SC_CTC_LIN");
@@ -1217,10 +1097,10 @@ static int lin_ppl(int Umax) {
 // a 1024-thread group
 static int ab_halo_k(int Umax) {
   auto waves = [&](int K) { return (Umax + 1 + (64 - K) - 1) / (64 - K); };
-  for (int K : {SC_CTC_KMAX, 4, 2, 1})
+  for (int K : {kCtcKmax, 4, 2, 1})
     if (waves(K) <= 16) {
       // a wider halo with the same wave count: fewer exchanges (barriers) per step
-      if (SC_CTC_KMAX == 16 && K == 16 && waves(24) == waves(16)) return 24;
+      if (K == 16 && waves(24) == waves(16)) return 24;
       return K;
     }
   return 0;
@@ -1396,10 +1276,8 @@ static void launch_ab(const CtcArgs& a, hipStream_t st) {
   const int nw = (a.Umax + 1 + (64 - K) - 1) / (64 - K);
   const size_t sh = 2 * (size_t)nw * (64 - K) * sizeof(float2);
   switch (K) {
-#if SC_CTC_KMAX == 16
     case 24: hipLaunchKernelGGL((ctc_ab_kernel<24>), dim3(2 * a.B), dim3(64 * nw), sh, st, a); break;
     case 16: hipLaunchKernelGGL((ctc_ab_kernel<16>), dim3(2 * a.B), dim3(64 * nw), sh, st, a); break;
-#endif
     case 8: hipLaunchKernelGGL((ctc_ab_kernel<8>), dim3(2 * a.B), dim3(64 * nw), sh, st, a); break;
     case 4: hipLaunchKernelGGL((ctc_ab_kernel<4>), dim3(2 * a.B), dim3(64 * nw), sh, st, a); break;
     case 2: hipLaunchKernelGGL((ctc_ab_kernel<2>), dim3(2 * a.B), dim3(64 * nw), sh, st, a); break;

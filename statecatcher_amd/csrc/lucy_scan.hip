@@ -47,28 +47,12 @@
 
 namespace sc {
 
-// SC_ABL: ablation bitmask for tools/abl_bench.sh only (never set in a shipped build):
-//   1 trivial gate-gradient math, 2 no dgates stores, 4 no cross-wave compositions,
-//   8 backward barriers B1-B3 removed (wrong results; timing only)
-#ifndef SC_ABL
-#define SC_ABL 0
-#endif
-// SC_SCAN_LW (forward): retire the next super-chunk's gate DMA at the END of the current one
-// (just before its own output stores) instead of before its second barrier, so the DMA has the
-// whole super-chunk to land.  (The backward keeps its wait before B2: its checkpoint rows are one
-// shared copy that other waves read after B2, and per-wave copies measured 3% slower in-step.)  The slots are wave-private: the issuing wave's own vmcnt orders its later
-// ds_reads, no barrier needed (MI355X_MICROARCH.md item 7).  SC_FWD_FD: LDS slots per wave in the
-// forward (2: two super-chunks in flight, 16-bit gates).  SC_FWD_CSW: forward prefix
-// compositions with the wave's position as a compile-time count (one LDS round trip).
-#ifndef SC_SCAN_LW
-#define SC_SCAN_LW 1
-#endif
-#ifndef SC_FWD_FD
-#define SC_FWD_FD 1
-#endif
-#ifndef SC_FWD_CSW
-#define SC_FWD_CSW 0
-#endif
+// The forward retires the next super-chunk's gate DMA at the END of the current one (just before
+// its own output stores) instead of before its second barrier, so the DMA has the whole
+// super-chunk to land.  The slots are wave-private: the issuing wave's own vmcnt orders its later
+// ds_reads, no barrier needed (MI355X_MICROARCH.md item 7).  (The backward keeps its wait before
+// B2: its checkpoint rows are one shared copy that other waves read after B2, and per-wave copies
+// measured 3% slower in-step.)
 
 constexpr int kChunk = 64;
 typedef uint32_t v4u __attribute__((ext_vector_type(4)));   // time steps per super-chunk (== NW * LC for every variant)
@@ -325,28 +309,6 @@ __device__ __forceinline__ float compose_suffix(const float2 (*agg)[64], int lan
   return x;
 }
 
-// Prefix composition with the wave's position as a compile-time count: one uniform branch picks
-// the instance, whose W map fetches all issue before the first link (one LDS round trip instead
-// of one per group of four).  Forward only: the backward has no registers for 2 W map values.
-template <int W>
-__device__ __forceinline__ float prefix_fixed(const float2 (*agg)[64], int lane, float x) {
-  if constexpr (W > 0) {
-    float2 m[W];
-#pragma unroll
-    for (int q = 0; q < W; ++q) m[q] = agg[q][lane];
-#pragma unroll
-    for (int q = 0; q < W; ++q) x = fmaf(m[q].x, x, m[q].y);
-  }
-  return x;
-}
-template <int NW, int W = 0>
-__device__ __forceinline__ float compose_prefix_sw(const float2 (*agg)[64], int lane, int w, float x) {
-  if constexpr (W == NW - 1)
-    return prefix_fixed<W>(agg, lane, x);
-  else
-    return w == W ? prefix_fixed<W>(agg, lane, x) : compose_prefix_sw<NW, W + 1>(agg, lane, w, x);
-}
-
 // ------------------------------------------------------------------------ forward ----------
 // Reductions over aligned groups of N lanes (N = 2, 4, 8, 16) through DPP: every lane of a group
 // ends with the group's sum.
@@ -540,7 +502,7 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
     lds_barrier();
     float s = carS[k & 1][lane];
     const float s_in = s;
-    s = SC_FWD_CSW ? compose_prefix_sw<NW>(aggS, lane, w, s) : compose_prefix<NW>(aggS, lane, w, s);
+    s = compose_prefix<NW>(aggS, lane, w, s);
 #pragma unroll
     for (int j = 0; j < LC; ++j) {
       s = fmaf(dec[j >> 1][j & 1], s, u[j >> 1][j & 1]);
@@ -559,11 +521,10 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
     }
     if (w == NW - 1) carS[(k + 1) & 1][lane] = s;
     aggH[w][lane] = make_float2(Ah, Bh);
-    if (!SC_SCAN_LW) wait_next(k);   // super-chunk k+1 has landed in this wave's slot
     lds_barrier();
     float h = carH[k & 1][lane];
     const float h_in = h;
-    h = SC_FWD_CSW ? compose_prefix_sw<NW>(aggH, lane, w, h) : compose_prefix<NW>(aggH, lane, w, h);
+    h = compose_prefix<NW>(aggH, lane, w, h);
     float hs[LC];
 #pragma unroll
     for (int j = 0; j < LC; ++j) {
@@ -571,9 +532,9 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
       hs[j] = h;
     }
     if (w == NW - 1) carH[(k + 1) & 1][lane] = h;
-    // late wait: retire super-chunk k+1's DMA before this super-chunk's own stores (a store
-    // issued before a full vmcnt wait would be drained with it)
-    if (SC_SCAN_LW) wait_next(k);
+    // late wait: super-chunk k+1 has landed in this wave's slot, retired before this
+    // super-chunk's own stores (a store issued before a full vmcnt wait would be drained with it)
+    wait_next(k);
     if (w == 0 && a.ckpt && dok) {
       a.ckpt[((int64_t)(b * a.nsc + k) * 2) * a.D + d] = s_in;
       a.ckpt[((int64_t)(b * a.nsc + k) * 2 + 1) * a.D + d] = h_in;
@@ -895,9 +856,8 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     }
     aggA[w][lane] = make_float2(As, Bs);
     aggC[w][lane] = make_float2(Ph, Qh);
-    if (!(SC_ABL & 8)) lds_barrier();                          // B1
-    float s = s_ck;
-    if (!(SC_ABL & 4)) s = compose_prefix<NW>(aggA, lane, w, s);
+    lds_barrier();                                             // B1
+    float s = compose_prefix<NW>(aggA, lane, w, s_ck);
     // s chain (serial), then c = tanh(hn + s) and (1 - zg) c two steps per instruction
 #pragma unroll
     for (int j = 0; j < LC; ++j) {
@@ -917,8 +877,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
       Ah *= zg[j >> 1][j & 1];
       Bh = fmaf(zg[j >> 1][j & 1], Bh, wz[j >> 1][j & 1]);
     }
-    float C = carGh[it & 1][lane];
-    if (!(SC_ABL & 4)) C = compose_suffix<NW>(aggC, lane, w, C);
+    float C = compose_suffix<NW>(aggC, lane, w, carGh[it & 1][lane]);
 #pragma unroll
     for (int j = LC - 1; j >= 0; --j) {
       u[j >> 1][j & 1] = dj[j >> 1][j & 1] + C;                // Gh_t
@@ -940,8 +899,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     aggD[w][lane] = make_float2(Ps, Qs);
     dma_wait();                   // the next super-chunk (and its checkpoint) has landed
     lds_barrier();                                             // B2
-    float h = h_ck;
-    if (!(SC_ABL & 4)) h = compose_prefix<NW>(aggB, lane, w, h);
+    float h = compose_prefix<NW>(aggB, lane, w, h_ck);
 #pragma unroll
     for (int j = 0; j < LC; ++j) {
       if constexpr (NBUF == 2)
@@ -950,8 +908,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
         hv[j >> 1][j & 1] = h;
       h = fmaf(zg[j >> 1][j & 1], h, wz[j >> 1][j & 1]);
     }
-    float Cs = carGs[it & 1][lane];
-    if (!(SC_ABL & 4)) Cs = compose_suffix<NW>(aggD, lane, w, Cs);
+    float Cs = compose_suffix<NW>(aggD, lane, w, carGs[it & 1][lane]);
     f2 gsj[LP];
 #pragma unroll
     for (int j = LC - 1; j >= 0; --j) {   // the serial part of the Gs scan
@@ -978,10 +935,6 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
         for (int g = 0; g < 7; ++g) g7[g] = f2{rg[jp][g], rg[jp + 1][g]};
         gate_grads2(g7[0], g7[1], g7[2], g7[3], g7[4], g7[5], g7[6], zg[p], dec[p], u[p], dp[p],
                     gsj[p], hv[p], sv[p], x[p], o);
-      }
-      if (SC_ABL & 1) {
-#pragma unroll
-        for (int g = 0; g < 7; ++g) o[g] = gsj[p];
       }
       if constexpr (FULL && NBUF == 2) {
 #pragma unroll
@@ -1013,7 +966,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
               const float og = o[g][h2];
               const T ogt = E::st(LN ? og * lrs[h2] : og);
               if constexpr (WST) ((T*)slot)[(j * 7 + g) * 64 + lane] = ogt;   // over its raw gate
-              else if (!(SC_ABL & 2)) dgbuf.st(ogt, vo, so + (uint32_t)(g * a.dg_cd * sizeof(T)));
+              else dgbuf.st(ogt, vo, so + (uint32_t)(g * a.dg_cd * sizeof(T)));
               if constexpr (NBUF == 1) bacc1[g] += E::ld(ogt);
               else if constexpr (!FULL) bacc[g][h2] += og;
             }
@@ -1029,7 +982,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
         if (SP % 64 == 0 || p < SP) {
           const int row = p >> 3, pc = p & 7;
           const int j = row / 7, g = row - 7 * (row / 7);
-          if ((FULL || (t0 + j < a.T && pc <= pcmax)) && !(SC_ABL & 2)) {
+          if (FULL || (t0 + j < a.T && pc <= pcmax)) {
             const v4u v = *(const v4u*)(slot + p * 16);
             if constexpr (FULL)   // lane offset from the gate DMA table, time in soffset
               __builtin_amdgcn_raw_buffer_store_b128(v, dgbuf.r, voffT[i][lane],
@@ -1080,14 +1033,9 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
 
 // ------------------------------------------------------------------------ launchers --------
 // 16 waves x 4 steps per wave (one 16-wave workgroup per CU at B*D/64 = 256), every dtype.
-#ifndef SC_FWD_NW
-#define SC_FWD_NW 16
-#endif
-constexpr int kNW = SC_FWD_NW, kLC = kChunk / SC_FWD_NW;
-#ifndef SC_BWD_NW
-#define SC_BWD_NW 8
-#endif
-constexpr int kBNW = SC_BWD_NW, kBLC = kChunk / SC_BWD_NW;
+// The backward: 8 waves x 8 steps.
+constexpr int kNW = 16, kLC = kChunk / kNW;
+constexpr int kBNW = 8, kBLC = kChunk / kBNW;
 
 // > 64 KiB of dynamic LDS must be opted into per kernel (gfx950 has 160 KiB per CU).  Called
 // once per kernel instantiation (function-local static): the call costs host time per launch.
@@ -1100,7 +1048,7 @@ static bool set_lds_limit(K kernel, size_t bytes) {
 template <int DT, int PW, bool SPLIT = false, int LN = 0, int NB = 8>
 static void launch_fwd(const ScanFwdArgs& a, hipStream_t st) {
   using T = typename Elem<DT>::T;
-  constexpr int FD = (SC_FWD_FD >= 2 && LdsElem<T, PW>::BYTES == 2) ? 2 : 1;   // 2 x 56 KiB fit
+  constexpr int FD = 1;   // one LDS slot per wave
   auto kern = lucy_scan_fwd_kernel<DT, kNW, kLC, PW, FD, SPLIT, LN, NB>;
   const size_t lds = (size_t)FD * kNW * kLC * 7 * 64 * LdsElem<T, PW>::BYTES;
   static const bool lds_ok = set_lds_limit(kern, lds);

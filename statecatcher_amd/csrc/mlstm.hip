@@ -31,20 +31,6 @@
 
 #include "sc_common.h"
 
-// SC_ML_ABL: timing ablations (tools/mlstm_abl.sh; results are garbage).  Forward walk: 1 no S
-// MFMAs, 2 no H MFMAs, 4 no state-update MFMAs, 8 no global stores, 16 no LDS fill.  Backward
-// walk: 32 no A/dA phase, 64 no dq phase, 128 no dk/dv phase, 256 no dC update, 512 no loads,
-// 1024 no dq role (its workgroups exit), 2048 no walk role; per-operand loads of the backward
-// (both roles, for FETCH_SIZE differences): 4096 q, 8192 k, 16384 v, 32768 dh, 65536 h,
-// 131072 the dq role's state image; 262144 no dq / dk / dv stores.
-#ifndef SC_ML_ABL
-#define SC_ML_ABL 0
-#endif
-#ifndef SC_ML_XCDH
-#define SC_ML_XCDH 1
-#endif
-#define ML_ABL(b) ((SC_ML_ABL & (b)) != 0)
-
 namespace sc {
 
 namespace {
@@ -384,26 +370,24 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
     const ChunkGates G = chunk_gate_math(pig, pfg, m, a.scale, lane);
     if (k > 0 && tid < DQ) n = decay * n + np2[tid] + np2[DQ + tid];   // previous chunk's update
     decay = G.decay;
-    if (!ML_ABL(16)) {
 #pragma unroll
-      for (int u = 0; u < NQP; ++u) {
-        const int e = tid + 256 * u, r = e / (DQ / 8), c = (e % (DQ / 8)) * 8;
-        if (kOut) *(V8*)(Qs + r * LQ + c) = cvt8<DT, IO>(pq[u]);
-        const V8 x = cvt8<DT, IO>(pk[u]);
-        *(V8*)(Ks + r * LQ + c) = x;
-        {
-          const float f = __shfl(G.fs, r);
-          V8 y;
+    for (int u = 0; u < NQP; ++u) {
+      const int e = tid + 256 * u, r = e / (DQ / 8), c = (e % (DQ / 8)) * 8;
+      if (kOut) *(V8*)(Qs + r * LQ + c) = cvt8<DT, IO>(pq[u]);
+      const V8 x = cvt8<DT, IO>(pk[u]);
+      *(V8*)(Ks + r * LQ + c) = x;
+      {
+        const float f = __shfl(G.fs, r);
+        V8 y;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) y[j] = (T)((float)x[j] * f);
-          *(V8*)(Kf + r * LQ + c) = y;
-        }
+        for (int j = 0; j < 8; ++j) y[j] = (T)((float)x[j] * f);
+        *(V8*)(Kf + r * LQ + c) = y;
       }
+    }
 #pragma unroll
-      for (int u = 0; u < NVP; ++u) {
-        const int e = tid + 256 * u, r = e / (kCB / 8), c = (e % (kCB / 8)) * 8;
-        *(V8*)(Vs + r * LC + c) = cvt8<DT, IO>(pv[u]);
-      }
+    for (int u = 0; u < NVP; ++u) {
+      const int e = tid + 256 * u, r = e / (kCB / 8), c = (e % (kCB / 8)) * 8;
+      *(V8*)(Vs + r * LC + c) = cvt8<DT, IO>(pv[u]);
     }
     if (w == 0) {
       if constexpr (kOut) {
@@ -444,7 +428,7 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
 #pragma unroll
       for (int u = 0; u < NCP; ++u) {
         const int e = tid + 256 * u, j = e / (DQ / 8), c = (e % (DQ / 8)) * 8;
-        if (!ML_ABL(8)) *(u32x4*)(Cs + j * DQ + c) = *(const u32x4*)(CT + j * LQ + c);
+        *(u32x4*)(Cs + j * DQ + c) = *(const u32x4*)(CT + j * LQ + c);
       }
     }
     // MODE 1: the next chunk's loads go out AFTER this chunk's stores.  vmcnt retires in order, so
@@ -482,7 +466,7 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
         for (int kk = 0; kk < DQ / 32; ++kk) kb[kk] = frag<V8, T>(Ks, LQ, 16 * ct, 32 * kk, lane);
         f32x4 s4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kk = 0; kk < (ML_ABL(1) ? 0 : DQ / 32); ++kk) s4 = M::mma(qa[kk], kb[kk], s4);
+        for (int kk = 0; kk < DQ / 32; ++kk) s4 = M::mma(qa[kk], kb[kk], s4);
         const int s = 16 * ct + (lane & 15);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -529,9 +513,9 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
         for (int kk = 0; kk < DQ / 32; ++kk) cb2[kk] = frag<V8, T>(CT, LQ, 16 * cj, 32 * kk, lane);
         f32x4 h4 = {0.f, 0.f, 0.f, 0.f}, e4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kk = 0; kk < (ML_ABL(2) ? 0 : 2); ++kk) h4 = M::mma(ma[kk], vb[kk], h4);
+        for (int kk = 0; kk < 2; ++kk) h4 = M::mma(ma[kk], vb[kk], h4);
 #pragma unroll
-        for (int kk = 0; kk < (ML_ABL(2) ? 0 : DQ / 32); ++kk) e4 = M::mma(qa[kk], cb2[kk], e4);
+        for (int kk = 0; kk < DQ / 32; ++kk) e4 = M::mma(qa[kk], cb2[kk], e4);
 #pragma unroll
         for (int r = 0; r < 4; ++r) hv[cj][r] = (h4[r] + rf[r] * e4[r]) * zi[r];
         __builtin_amdgcn_sched_barrier(0);
@@ -545,7 +529,7 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
 #pragma unroll
       for (int u = 0; u < 2; ++u) {   // 16 rows x 128 bytes = 128 pieces over 64 lanes
         const int e = lane + 64 * u, t = 16 * w + (e >> 3), c = (e & 7) * 8;
-        if (!ML_ABL(8)) *(u32x4*)(H + (t0 + t) * DV + cj0 + c) = *(const u32x4*)(Ms + t * LC + c);
+        *(u32x4*)(H +(t0 + t) * DV + cj0 + c) = *(const u32x4*)(Ms + t * LC + c);
       }
       if (cb == 0 && lane < 16) {   // the wave's own rows
         const int t = 16 * w + lane;
@@ -560,7 +544,7 @@ __global__ void __launch_bounds__(256, 2) mlstm_fw_walk(MArgs a) {
       const int q = w + 4 * p, i0 = 16 * (q / TJ), j0 = 16 * (q % TJ);
       f32x4 c = acc[p];
 #pragma unroll
-      for (int kk = 0; kk < (ML_ABL(4) ? 0 : kL / 32); ++kk)
+      for (int kk = 0; kk < kL / 32; ++kk)
         c = M::mma(frag_t<V8, T>(Kf, LQ, 32 * kk, i0, lane),
                    frag_t<V8, T>(Vs, LC, 32 * kk, j0, lane), c);
       acc[p] = c;
@@ -831,14 +815,14 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
   constexpr int UQ = (NQ8 + 511) / 512, UV = (NV8 + 511) / 512, UC = (NC8 + 511) / 512;
   constexpr int UH = DV / 64;   // dh / h pieces per thread (8 threads per row)
   const bool walk = (int)blockIdx.x < a.BH;
-  // sequence of this workgroup.  SC_ML_XCDH: the NH heads of one batch row on one XCD (bids go
+  // sequence of this workgroup: the NH heads of one batch row on one XCD (bids go
   // round-robin over the 8 XCDs): in the xLSTM layer's fused gradient [B][T][N] the heads' dq /
   // dk / dv segments of a time step share cache lines (192 / 384-byte segments at a 4,624-byte
   // row pitch), and lines that heads on different XCDs write in parts reach HBM as partial lines
   // the L2s must first read (90.9 MB of FETCH per launch at C4, r6m2).  Both roles keep sharing
   // their XCD (workgroups i and BH + i, BH % 8 == 0).
   int bh = walk ? blockIdx.x : blockIdx.x - a.BH;
-  if (SC_ML_XCDH && a.NH > 1 && a.BH % 8 == 0 && (a.BH / 8) % a.NH == 0) {
+  if (a.NH > 1 && a.BH % 8 == 0 && (a.BH / 8) % a.NH == 0) {
     const int x = bh % 8, kk = bh / 8;
     bh = (x + 8 * (kk / a.NH)) * a.NH + kk % a.NH;
   }
@@ -865,10 +849,8 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     const T* h = (const T*)a.h + ro * DV;
 #pragma unroll
     for (int u = 0; u < UH; ++u) {
-      if (!ML_ABL(512)) {
-        if (!ML_ABL(32768)) rd[u] = *(const u32x4*)(dh + (tid & 7) * 8 + 64 * u);
-        if (!ML_ABL(65536)) rh[u] = *(const u32x4*)(h + (tid & 7) * 8 + 64 * u);
-      }
+      rd[u] = *(const u32x4*)(dh + (tid & 7) * 8 + 64 * u);
+      rh[u] = *(const u32x4*)(h + (tid & 7) * 8 + 64 * u);
     }
     m_t = a.mrow[ro];
     dv_ = a.den[ro];
@@ -885,15 +867,15 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
     for (int u = 0; u < UQ; ++u) {
       const int e = tid + 512 * u, r = e / (DQ / 8), c = (e % (DQ / 8)) * 8;
-      if (e < NQ8 && !ML_ABL(512)) {
-        if (!ML_ABL(4096)) rq[u] = *(const u32x4*)(Qg + (tb + r) * a.qt + c);
-        if (!ML_ABL(8192)) rk[u] = *(const u32x4*)(Kg + (tb + r) * a.qt + c);
+      if (e < NQ8) {
+        rq[u] = *(const u32x4*)(Qg + (tb + r) * a.qt + c);
+        rk[u] = *(const u32x4*)(Kg + (tb + r) * a.qt + c);
       }
     }
 #pragma unroll
     for (int u = 0; u < UV; ++u) {
       const int e = tid + 512 * u, r = e / (DV / 8), c = (e % (DV / 8)) * 8;
-      if (e < NV8 && !ML_ABL(512) && !ML_ABL(16384)) rv[u] = *(const u32x4*)(Vg + (tb + r) * a.vt + c);
+      if (e < NV8) rv[u] = *(const u32x4*)(Vg + (tb + r) * a.vt + c);
     }
   };
   // gate quantities (every wave, lane = step) and the Q / K (/ Qr) / V fill; returns g = b_{L-1}
@@ -1028,8 +1010,6 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     }
   };
 
-  if (ML_ABL(1024) && !walk) return;
-  if (ML_ABL(2048) && walk) return;
   if (!walk) {
     // ================= dq role: every chunk of sequence bh, independently =================
     TI* dQg = (TI*)a.dq + qrow(a, bh, 0);
@@ -1047,7 +1027,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
       for (int u = 0; u < UC; ++u) {
         const int e = tid + 512 * u;
-        if (e < NC8 && !ML_ABL(512) && !ML_ABL(131072)) rc[u] = *(const u32x4*)(Ck + 8 * e);
+        if (e < NC8) rc[u] = *(const u32x4*)(Ck + 8 * e);
       }
       const float n_k = tid < DQ ? a.ns[((int64_t)bh * (a.nc + 1) + k) * DQ + tid] : 0.0f;
       load_qkv(k);
@@ -1069,13 +1049,13 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
       __syncthreads();
       // ---- dA = W o (Dn V^T + dden): 10 causal tiles ----
 #pragma unroll 1
-      for (int jb = w; jb < (ML_ABL(32) ? 0 : 10); jb += 8) a_job(jb, false);
+      for (int jb = w; jb < 10; jb += 8) a_job(jb, false);
       __syncthreads();
       const float inv = 1.0f / Sk;
       // ---- dq = dA K + rowf (Dn C~_k^T + dden n~_k): 4 x NI tiles, wave w the row block
       // tr = w >> 1 and NI / 2 column blocks: each A fragment feeds NI / 2 MFMAs.  (The causal
       // chain always takes both k-steps: dA's tiles above the diagonal are zero.) ----
-      if (!ML_ABL(64)) {
+      {
         constexpr int NC2 = NI / 2;
         const int tr = w >> 1, c0 = (w & 1) * NC2;
         f32x4 d4[NC2], e4[NC2];
@@ -1104,8 +1084,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int tt = 16 * tr + 4 * (lane >> 4) + r;
             const float v = d4[c][r] + rowf[tt] * (e4[c][r] + dden[tt] * nki);
-            if (!ML_ABL(262144))
-              dQg[(t0 + tt) * a.qt + i] = out16<DT, IO>(v * inv);
+            dQg[(t0 + tt) * a.qt + i] = out16<DT, IO>(v * inv);
             qd[r] = sum16(v * (float)Qs[tt * LQ + i]);
           }
           if ((lane & 15) == 0) {
@@ -1195,14 +1174,14 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     if (k > 0) load_rows(k - 1);   // dh / h of this chunk are consumed
     // ---- A = W o (Q K^T) and dA = W o (Dn V^T + dden): 10 causal tiles each, 20 jobs ----
 #pragma unroll 1
-    for (int jb = w; jb < (ML_ABL(32) ? 0 : 20); jb += 8) a_job(jb < 10 ? jb : jb - 10, jb < 10);
+    for (int jb = w; jb < 20; jb += 8) a_job(jb < 10 ? jb : jb - 10, jb < 10);
     __syncthreads();
     if (k > 0) load_qkv(k - 1);
     const float inv = 1.0f / S;
     // ---- dk = dA^T Q + es (V dC~^T + dn~): 4 x NI tiles; dv = A^T Dn + es (K dC~): 4 x NJ.
     // Wave w: key row block sr = w >> 1, NI / 2 dk column blocks, then NJ / 2 dv column blocks
     // in passes of NI / 2 (register-blocked: each A fragment feeds NI / 2 MFMAs) ----
-    if (!ML_ABL(128)) {
+    {
       constexpr int NC2 = NI / 2;
       const int sr = w >> 1;
       {
@@ -1233,8 +1212,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
           for (int r = 0; r < 4; ++r) {
             const int s = 16 * sr + 4 * (lane >> 4) + r;
             const float v = d4[c][r] + es[s] * (e4[c][r] + dni);
-            if (!ML_ABL(262144))
-              dKg[(t0 + s) * a.qt + i] = out16<DT, IO>(v * inv);
+            dKg[(t0 + s) * a.qt + i] = out16<DT, IO>(v * inv);
             kd[r] = sum16(v * (float)Ks[s * LQ + i]);
           }
           if ((lane & 15) == 0) {
@@ -1271,8 +1249,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int s = 16 * sr + 4 * (lane >> 4) + r;
-            if (!ML_ABL(262144))
-              dVg[(t0 + s) * a.vt + j] = out16<DT, IO>((d4[c][r] + es[s] * e4[c][r]) * inv);
+            dVg[(t0 + s) * a.vt + j] = out16<DT, IO>((d4[c][r] + es[s] * e4[c][r]) * inv);
           }
         }
       }
@@ -1281,7 +1258,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
     for (int p = 0; p < PC; ++p) acc[p] *= decay;
 #pragma unroll
-    for (int kk = 0; kk < (ML_ABL(256) ? 0 : kL / 32); ++kk) {
+    for (int kk = 0; kk < kL / 32; ++kk) {
       V8 fq[BI], fd[BJ];
 #pragma unroll
       for (int x = 0; x < BI; ++x) fq[x] = frag_t<V8, T>(Qr, LQ, 32 * kk, 16 * (ib0 + x), lane);

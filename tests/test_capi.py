@@ -57,6 +57,12 @@ def test_invalid_arguments_rejected_without_gpu(lib):
     assert rc == -1 and b"exceeds" in lib.sc_last_error()
     rc = lib.sc_ctc_fwd(null, 0, 1, 1, 1, 4, 4, 4, null, 0, 1, null, null, 9, null, null, 0, null)
     assert rc == -1 and b"blank" in lib.sc_last_error()
+    # sc_gemm_tn_bf16: only the tile codes 0 / 128 / 192 / 256 / 257 exist (the pointers are never
+    # dereferenced: validation fails before any launch)
+    p = ctypes.c_void_p(4096)
+    for tile_m in (1, 2, 3):
+        rc = lib.sc_gemm_tn_bf16(p, 64, p, 64, p, 256, 64, 256, 64, tile_m, null)
+        assert rc == -1 and b"tile_m" in lib.sc_last_error()
     # empty problems are no-ops
     assert lib.sc_lucy_scan_fwd(null, 0, null, null, null, null, null, null, 0, 5, 5, 1, 1, 1, 64, 1, 1, null, null) == 0
     assert lib.sc_ctc_greedy_decode(null, 0, 0, 5, 5, 1, 1, null, 0, null, null, null) == 0
