@@ -19,14 +19,8 @@
 //                     tools/ctc_precision.py)
 //   ctc_chain_kernel  per b: for every target position the next position with the same label,
 //                     so label occupancies are summed in a fixed order (deterministic, no atomics)
-//   ctc_lin_kernel    (Umax <= 255, SC_CTC_LIN=1) the lattice in linear probability space, fp64,
-//                     renormalised every 16 steps by exact powers of two: five full-rate fp64
-//                     adds / multiplies per state pair and step instead of five exp2 / log2; one
-//                     wave computes, two more store its rows as fp32 logs (lin_produce /
-//                     lin_consume); a sequence with an emission or a wave that would underflow
-//                     goes to ctc_x64_kernel
-//   ctc_ab_kernel     (the default) one workgroup per (sequence, direction): 2B workgroups run alpha forward
-//                     and beta backward concurrently.  Two states (a blank and its label) per
+//   ctc_ab_kernel     one workgroup per (sequence, direction): 2B workgroups run alpha forward and
+//                     beta backward concurrently.  Two states (a blank and its label) per
 //                     lane; each wave also carries a K-pair halo of its neighbour's pairs so it
 //                     advances K steps with DPP wave_shr:1 / wave_shl:1 only (no LDS, no
 //                     barrier), then exchanges halos through LDS.  Emission rows are prefetched
@@ -64,9 +58,6 @@ struct CtcWs {
   double* ll2s;   // [B]        base-2 log-likelihood of the SHIFTED lattice (log2 p - sum_t c_t)
   int* chain;     // [B,Um]
   int* first;     // [B,Um]
-  // one-wave family (Umax <= 255) only:
-  float* ylin;    // [B,T,Sp]   linear shifted emissions 2^(lpe) (0: dead)
-  int* flag;      // [B]        a live emission below 2^-kTiny: the linear lattice is not used
   int* sharp;     // [B]        the log-space lattice drifted more than kDrift bits between two
                   //            re-centrings: ctc_x64_kernel recomputes the sequence exactly
 };
@@ -76,13 +67,10 @@ static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 // states per lane for a given max state count
 static int states_per_lane(int S) { return (S + 63) / 64; }
 
-static int lin_ppl(int Umax);
-
 static size_t ws_layout(int B, int T, int Umax, CtcWs* w, void* base) {
   const int S = 2 * Umax + 1;
   const int Sp = 64 * states_per_lane(S);
-  const bool lin = lin_ppl(Umax) > 0;
-  const size_t ab = 4;   // alpha / beta: fp32 base-2 log rows (every lattice)
+  const size_t ab = 4;   // alpha / beta: fp32 base-2 log rows (both lattices)
   const int Um = Umax > 0 ? Umax : 1;
   char* p = (char*)base;
   size_t off = 0;
@@ -103,8 +91,6 @@ static size_t ws_layout(int B, int T, int Umax, CtcWs* w, void* base) {
   t.ll2s = (double*)take((size_t)B * 8);
   t.chain = (int*)take((size_t)B * Um * 4);
   t.first = (int*)take((size_t)B * Um * 4);
-  t.ylin = lin ? (float*)take((size_t)B * T * Sp * 4) : nullptr;
-  t.flag = lin ? (int*)take((size_t)B * 4) : nullptr;
   t.sharp = (int*)take((size_t)B * 4);
   if (w) *w = t;
   return off;
@@ -122,7 +108,6 @@ struct CtcArgs {
   const void* x;
   int is_logits, B, T, V, S, Sp, Umax, blank;
   int kh;   // steps between halo exchanges of ctc_ab_kernel (re-centring every 2 kh steps)
-  int lin;      // the linear-domain lattice (ctc_lin_kernel) runs
   int64_t sb, stt;
   const int64_t* tg;
   int64_t tgs;
@@ -150,8 +135,6 @@ __device__ __forceinline__ int state_label(const int64_t* tg, int s, int blank, 
 }
 
 // ---------------------------------------------------------------------------- emissions -----
-constexpr float kTiny = 120.0f;   // (2^-120: a normal fp32 with 6 bits of headroom)
-
 template <int DT>
 __global__ void __launch_bounds__(256) ctc_emit_kernel(CtcArgs a) {
   using E = Elem<DT>;
@@ -238,27 +221,16 @@ __global__ void __launch_bounds__(256) ctc_emit_kernel(CtcArgs a) {
   }
   c = wave_max_dpp(c);
   if (!(c > -1e29f)) c = 0.0f;   // every state dead (or NaN): no shift, the sentinel stays
-  bool tiny = false;
-  auto put = [&](int s, float e) {
-    out[s] = e;
-    if (a.lin) {
-      // linear emission for ctc_lin_kernel; a live one below 2^-kTiny sends the sequence to the
-      // log-space lattice (fp32 would lose it, and it may carry every path)
-      tiny |= e > -1e29f && e < -kTiny;
-      a.ws.ylin[row * a.Sp + s] = e > -1e29f ? exp2_(e) : 0.0f;
-    }
-  };
   if (inreg) {
 #pragma unroll
     for (int j = 0; j < kGx; ++j) {
       const int s = lane + 64 * j;
-      if (s < a.Sp) put(s, s < Sb ? fmaxf(lp2x(xs[j]) - c, -1e30f) : -1e30f);
+      if (s < a.Sp) out[s] = s < Sb ? fmaxf(lp2x(xs[j]) - c, -1e30f) : -1e30f;
     }
   } else {
-    for (int s = lane; s < a.Sp; s += 64) put(s, s < Sb ? fmaxf(lp2(s) - c, -1e30f) : -1e30f);
+    for (int s = lane; s < a.Sp; s += 64) out[s] = s < Sb ? fmaxf(lp2(s) - c, -1e30f) : -1e30f;
   }
   if (lane == 0) a.ws.cst[row] = c;
-  if (a.lin && __ballot(tiny) && lane == 0) a.ws.flag[b] = 1;   // (every writer stores 1)
 }
 
 // ---------------------------------------------------------------------------- chains --------
@@ -544,291 +516,6 @@ __global__ void __launch_bounds__(1024) ctc_ab_kernel(CtcArgs a) {
   else ab_run<K, false>(a, b, Tb, Ub);
 }
 
-// The one-wave lattices (ctc_lin_kernel, ctc_x64_kernel) hold PPL pairs of states per lane
-// (PPL <= 4: U <= 255; C2's U <= 150 takes PPL = 3): lane l holds pairs p = l PPL .. l PPL +
-// PPL - 1, so a step needs one DPP lane shift and no halo, LDS or barrier.
-constexpr int kAb1R = 16;   // the linear lattice's renormalisation period (steps)
-constexpr int kAb1P = 16;   // its emission prefetch depth (steps)
-
-// Linear-domain lattice (SC_CTC_LIN=1, Umax <= 255).  The pair-per-lane layout above, but
-// the values are probabilities in fp64: one step of a pair is
-//   alpha:  B' = (B + L[p-1]) e(2p);          L' = (L + B + skip L[p-1]) e(2p+1)
-//   beta:   B' = (B + L) e(2p);               L' = (L + B[p+1] + skip L[p+1]) e(2p+1)
-// five fp64 adds / multiplies (gfx950's vector ALU issues them at the fp32 rate) instead of five
-// exp2 / log2 at the transcendental rate, and exact 0 is "dead" (the DPP shifts' bound_ctrl zero
-// is the right boundary value).  Every kAb1R steps the wave max is renormalised into [0.5, 1) by
-// an exact power of two (v_ldexp_f64: no rounding), its exponent added to the fp64 offset that
-// the gradient reads exactly as the log-space kernels' re-centring offsets.
-//
-// One workgroup of three waves per (sequence, direction).  Wave 0 runs the recurrence and
-// leaves each 16-step chunk of rows in an LDS slot; waves 1 and 2 turn the previous chunk into
-// fp32 base-2 logs (frexp exponent + v_log_f32 of the mantissa) and store it.  So wave 0 issues no
-// global store: its vmcnt holds only the emission prefetch (a wait for a prefetched row would
-// otherwise also wait for every older row store — one workgroup of one wave that stored its own
-// rows measured 217 us at C2, no faster than the multi-wave log-space kernel), and the rows
-// are the same fp32 log-space rows the gradient reads from every other lattice.
-// fp64 keeps 2^1022 of range below the wave max between renormalisations (fp32 log space keeps
-// all of it; a state 2^1022 below the max that later carries the likelihood is the one case the
-// two differ).  A sequence whose live emissions reach below 2^-kTiny (the emit kernel's flag), and
-// a direction whose wave max or final likelihood underflows to 0, are flagged (sharp[b]) and
-// recomputed by ctc_x64_kernel.
-__device__ __forceinline__ double dpp_shr1d(double v) {   // lane-1's value (lane 0: 0)
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x138, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x138, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-__device__ __forceinline__ double dpp_shl1d(double v) {   // lane+1's value (lane 63: 0)
-  const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), 0x130, 0xf, 0xf, true);
-  const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), 0x130, 0xf, 0xf, true);
-  return __hiloint2double(hi, lo);
-}
-typedef double d2v __attribute__((ext_vector_type(2)));
-
-constexpr int kLinC = kAb1P;   // steps per chunk (LDS slot)
-
-// base-2 log of a non-negative double as fp32 (0 -> the dead sentinel): exact exponent plus the
-// mantissa's v_log_f32
-__device__ __forceinline__ float log2d(double v) {
-  int e;
-  const double m = frexp(v, &e);
-  return v > 0.0 ? (float)e + log2_((float)m) : kDead;
-}
-
-// wave 0: the recurrence over chunks; returns false on underflow (log space then decides)
-template <int PPL, bool BETA>
-__device__ __forceinline__ bool lin_produce(const CtcArgs& a, int b, int Tb, int Ub, d2v* slots,
-                                            int* fail_lds) {
-  const int lane = threadIdx.x;
-  const int64_t* tg = a.tg + (int64_t)b * a.tgs;
-  const int npairs = a.Sp / 2;
-  double skip[PPL];
-  uint32_t vo[PPL];   // emission pair byte offsets (kDrop past the row)
-  constexpr uint32_t kDrop = 0x80000000u;
-#pragma unroll
-  for (int j = 0; j < PPL; ++j) {
-    const int p = lane * PPL + j;
-    bool sk = false;
-    if (p < Ub) {
-      const int lab = (int)tg[p];
-      if (!BETA) {
-        sk = p >= 1 && lab != a.blank && lab != (int)tg[p - 1];
-      } else if (p + 1 < Ub) {
-        const int l2 = (int)tg[p + 1];
-        sk = l2 != a.blank && l2 != lab;
-      }
-    }
-    skip[j] = sk ? 1.0 : 0.0;
-    vo[j] = p < npairs ? (uint32_t)(8 * p) : kDrop;
-  }
-  const uint32_t rowb = (uint32_t)(a.Sp * 4);
-  const __amdgpu_buffer_rsrc_t ers = __builtin_amdgcn_make_buffer_rsrc(
-      a.ws.ylin + (int64_t)b * a.T * a.Sp, 0, (int)(rowb * (uint32_t)a.T), 0x00020000);
-  double* offn = (BETA ? a.ws.offB : a.ws.offA) + (int64_t)b * (a.T + 1);
-  if (lane == 0) offn[0] = 0.0;
-  auto tstep = [&](int i) { return BETA ? Tb - 1 - i : i; };
-  f2v bufA[kLinC][PPL], bufB[kLinC][PPL];
-  auto load = [&](f2v (&buf)[kLinC][PPL], int i0) {
-#pragma unroll
-    for (int s = 0; s < kLinC; ++s) {
-      const uint32_t so = (uint32_t)tstep(min(i0 + s, Tb - 1)) * rowb;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j)
-        buf[s][j] = __builtin_bit_cast(f2v, __builtin_amdgcn_raw_buffer_load_b64(ers, vo[j], so, 0));
-    }
-  };
-  double vB[PPL], vL[PPL];
-#pragma unroll
-  for (int j = 0; j < PPL; ++j) vB[j] = vL[j] = 0.0;
-  double off = 0.0;
-  bool fail = false;
-  // one chunk of steps into slot (chunk & 1); false when the wave underflowed
-  auto body = [&](const f2v (&buf)[kLinC][PPL], int ci) __attribute__((always_inline)) {
-    d2v* slot = slots + (size_t)(ci & 1) * kLinC * PPL * 64;
-#pragma unroll
-    for (int s = 0; s < kLinC; ++s) {
-      const int i = ci * kLinC + s;
-      if (i >= Tb) break;
-      if (i == 0) {
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          const int p = lane * PPL + j;
-          vB[j] = (p <= Ub && p == (BETA ? Ub : 0)) ? (double)buf[s][j].x : 0.0;
-          vL[j] = (p < Ub && p == (BETA ? Ub - 1 : 0)) ? (double)buf[s][j].y : 0.0;
-        }
-      } else if (!BETA) {
-        double prevL[PPL];
-        prevL[0] = dpp_shr1d(vL[PPL - 1]);
-#pragma unroll
-        for (int j = 1; j < PPL; ++j) prevL[j] = vL[j - 1];
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          const double nb = (vB[j] + prevL[j]) * (double)buf[s][j].x;
-          const double nl = __builtin_fma(skip[j], prevL[j], vL[j] + vB[j]) * (double)buf[s][j].y;
-          vB[j] = nb;
-          vL[j] = nl;
-        }
-      } else {
-        double nB[PPL], nL[PPL];
-        nB[PPL - 1] = dpp_shl1d(vB[0]);
-        nL[PPL - 1] = dpp_shl1d(vL[0]);
-#pragma unroll
-        for (int j = 0; j + 1 < PPL; ++j) {
-          nB[j] = vB[j + 1];
-          nL[j] = vL[j + 1];
-        }
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          const double nb = (vB[j] + vL[j]) * (double)buf[s][j].x;
-          const double nl = __builtin_fma(skip[j], nL[j], vL[j] + nB[j]) * (double)buf[s][j].y;
-          vB[j] = nb;
-          vL[j] = nl;
-        }
-      }
-      if ((i + 1) % kAb1R == 0) {   // renormalise the wave max to [0.5, 1)
-        double m = 0.0;
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) m = fmax(m, fmax(vB[j], vL[j]));
-        int e = 0;
-        (void)frexp(m, &e);
-        const float E = wave_max_dpp(m > 0.0 ? (float)e : -1e9f);
-        if (E < -1e8f) {   // every state underflowed (or the lattice died): log space instead
-          fail = true;
-          return;
-        }
-        const int ie = (int)E;
-#pragma unroll
-        for (int j = 0; j < PPL; ++j) {
-          vB[j] = ldexp(vB[j], -ie);
-          vL[j] = ldexp(vL[j], -ie);
-        }
-        off += (double)ie;
-        if (lane == 0) offn[(i + 1) / kAb1R] = off;
-      }
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) slot[(s * PPL + j) * 64 + lane] = d2v{vB[j], vL[j]};
-    }
-  };
-  const int nch = (Tb + kLinC - 1) / kLinC;
-  load(bufA, 0);
-  for (int ci = 0; ci < nch; ++ci) {
-    if (!fail) {
-      if ((ci & 1) == 0) {
-        if (ci + 1 < nch) load(bufB, (ci + 1) * kLinC);
-        body(bufA, ci);
-      } else {
-        if (ci + 1 < nch) load(bufA, (ci + 1) * kLinC);
-        body(bufB, ci);
-      }
-    }
-    if (lane == 0) *fail_lds = fail ? 1 : 0;
-    __syncthreads();   // chunk ci is in its slot (or the lattice failed); consumers take it
-  }
-  if (fail) return false;
-  if (!BETA) {
-    // P = alpha_{Tb-1}(2Ub) + alpha_{Tb-1}(2Ub-1), fixed-order fp64 sums
-    double c = 0.0;
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-      const int p = lane * PPL + j;
-      if (p == Ub) c += vB[j];
-      if (p == Ub - 1) c += vL[j];
-    }
-    double cs = 0.0;
-    for (int t = lane; t < Tb; t += 64) cs += (double)a.ws.cst[(int64_t)b * a.T + t];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      c += __shfl_xor(c, o);
-      cs += __shfl_xor(cs, o);
-    }
-    if (!(c > 0.0)) return false;   // underflowed at the end (or infeasible): log space decides
-    if (lane == 0) {
-      const double ll2s = log2(c) + off;
-      a.ws.ll2s[b] = ll2s;
-      a.nll[b] = (float)(-(ll2s + cs) * 0.6931471805599453);
-    }
-  }
-  return true;
-}
-
-// waves 1 and 2: chunk ci - 1's rows (slot (ci - 1) & 1) as fp32 base-2 logs into alpha / beta,
-// half of the chunk's steps each, while wave 0 computes chunk ci
-template <int PPL, bool BETA>
-__device__ __forceinline__ void lin_consume(const CtcArgs& a, int b, int Tb, const d2v* slots,
-                                            const int* fail_lds) {
-  const int lane = threadIdx.x & 63, half = (threadIdx.x >> 6) - 1;
-  const int npairs = a.Sp / 2;
-  constexpr uint32_t kDrop = 0x80000000u;
-  uint32_t vo[PPL];
-#pragma unroll
-  for (int j = 0; j < PPL; ++j) {
-    const int p = lane * PPL + j;
-    vo[j] = p < npairs ? (uint32_t)(8 * p) : kDrop;
-  }
-  const uint32_t rowb = (uint32_t)(a.Sp * 4);
-  const __amdgpu_buffer_rsrc_t ors = __builtin_amdgcn_make_buffer_rsrc(
-      (BETA ? a.ws.beta : a.ws.alpha) + (int64_t)b * a.T * a.Sp, 0, (int)(rowb * (uint32_t)a.T),
-      0x00020000);
-  const int nch = (Tb + kLinC - 1) / kLinC;
-  bool stop = false;
-  auto consume = [&](int ci) {
-    const d2v* slot = slots + (size_t)(ci & 1) * kLinC * PPL * 64;
-#pragma unroll
-    for (int s2 = 0; s2 < kLinC / 2; ++s2) {
-      const int s = half * (kLinC / 2) + s2, i = ci * kLinC + s;
-      if (i >= Tb) break;
-      const uint32_t so = (uint32_t)(BETA ? Tb - 1 - i : i) * rowb;
-#pragma unroll
-      for (int j = 0; j < PPL; ++j) {
-        const d2v v = slot[(s * PPL + j) * 64 + lane];
-        __builtin_amdgcn_raw_buffer_store_b64(
-            __builtin_bit_cast(__attribute__((ext_vector_type(2))) unsigned, f2v{log2d(v.x), log2d(v.y)}),
-            ors, vo[j], so, 0);
-      }
-    }
-  };
-  for (int ci = 0; ci < nch; ++ci) {
-    __syncthreads();   // chunk ci produced (wave 0); chunk ci - 1 consumed by both waves
-    if (!stop) stop = *fail_lds != 0;
-    if (!stop) consume(ci);
-  }
-}
-
-template <int PPL>
-__global__ void __launch_bounds__(192) ctc_lin_kernel(CtcArgs a) {
-  // two 16-step slots of PPL pairs x 64 lanes of (B, L) fp64
-  __shared__ d2v slots[2 * kLinC * PPL * 64];
-  __shared__ int fail_lds;
-  const bool is_beta = blockIdx.x >= a.B;
-  const int b = is_beta ? blockIdx.x - a.B : blockIdx.x;
-  const int Tb = clampi(a.in_lens[b], 0, a.T);
-  const int Ub = clampi(a.tgt_lens[b], 0, a.Umax);
-  const int w = uniform(threadIdx.x >> 6);
-  if (Tb == 0) {
-    if (!is_beta && threadIdx.x == 0) {
-      a.nll[b] = (Ub == 0) ? 0.0f : __builtin_huge_valf();
-      a.ws.ll2s[b] = (Ub == 0) ? 0.0 : -__builtin_huge_val();
-    }
-    return;
-  }
-  // (uniform over the workgroup: every wave takes the same branch, so the barriers match)
-  const bool tiny = a.ws.flag[b] != 0;
-  bool lin = !tiny;
-  if (lin) {
-    if (w == 0) {
-      lin = is_beta ? lin_produce<PPL, true>(a, b, Tb, Ub, slots, &fail_lds)
-                    : lin_produce<PPL, false>(a, b, Tb, Ub, slots, &fail_lds);
-    } else {
-      if (is_beta) lin_consume<PPL, true>(a, b, Tb, slots, &fail_lds);
-      else lin_consume<PPL, false>(a, b, Tb, slots, &fail_lds);
-      __builtin_amdgcn_s_waitcnt(0);   // (the stores retire before a fallback rewrites rows)
-    }
-    __syncthreads();
-  }
-  // an underflow (or a flagged emission): ctc_x64_kernel recomputes the sequence exactly
-  if (!lin && threadIdx.x == 0) a.ws.sharp[b] = 1;
-}
-
-
 // ------------------------------------------------- exact lattice for sharp sequences --------
 // ctc_x64_kernel recomputes, ONE wave per (sequence, direction), every sequence whose log-space
 // lattice drifted more than kDrift bits between two re-centrings (sharp[b], set by ctc_ab_kernel).
@@ -846,6 +533,9 @@ __global__ void __launch_bounds__(192) ctc_lin_kernel(CtcArgs a) {
 // 2^-53 of it).  Each step's row is stored as the fp32 base-2 log relative to that step's largest
 // exponent O_t (entry i + 1 of the offsets: the gradient reads a sharp sequence's offsets per
 // step), so the live states' stored values sit near 0 whatever the drift.
+// The only one-wave lattice: lane l holds the PPL pairs p = l PPL .. l PPL + PPL - 1 (PPL <= 4:
+// U <= 255; C2's U <= 150 takes PPL = 3), so a step needs one DPP lane shift and no halo, LDS or
+// barrier.
 constexpr int kXDeadE = -(1 << 29);
 constexpr int kX64P = 16;   // steps per emission prefetch chunk
 constexpr double kLog2eD = 1.4426950408889634;
@@ -1078,21 +768,6 @@ static int x64_ppl(int Umax) {
   return ppl <= 4 ? ppl : 0;
 }
 
-// pairs per lane of the one-wave lattice family (0: the multi-wave kernel).  Off unless
-// SC_CTC_LIN=1 in the environment.  Measured at C2 (tools/scan_bench.py --only ctc;
-// profiles/r4_lattice_ab.md): emit + chain + lattice 256 us against 211 us for the multi-wave
-// log-space kernel, and the gradient 60 us slower on the fp64 rows.  An ablation build without
-// the per-step stores ran 62 us faster: vmcnt retires loads and stores in issue order, so
-// waiting for a prefetched emission row also waits for the older row stores.
-static int lin_ppl(int Umax) {
-  static const bool on = [] {
-    const char* e = getenv("SC_CTC_LIN");
-    return e && e[0] == '1';
-  }();
-  const int ppl = (Umax + 1 + 63) / 64;
-  return (on && ppl <= 4) ? ppl : 0;
-}
-
 // K (steps between halo exchanges) so that ceil((Umax + 1) / (64 - K)) waves of state pairs fit
 // a 1024-thread group
 static int ab_halo_k(int Umax) {
@@ -1247,18 +922,11 @@ static void launch_ab(const CtcArgs& a, hipStream_t st);
 template <int DT>
 static void launch_fwd(const CtcArgs& a, hipStream_t st) {
   const int64_t rows = (int64_t)a.B * a.T;
-  if (a.lin) zero_async(a.ws.flag, (size_t)a.B * sizeof(int), st);   // tiny[b]
   hipLaunchKernelGGL((ctc_emit_kernel<DT>), dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, st, a);
   hipLaunchKernelGGL(ctc_chain_kernel, dim3(a.B, ((a.Umax > 0 ? a.Umax : 1) + 3) / 4), dim3(256), 0,
                      st, a);
-  switch (a.lin ? lin_ppl(a.Umax) : 0) {
-    case 1: hipLaunchKernelGGL((ctc_lin_kernel<1>), dim3(2 * a.B), dim3(192), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((ctc_lin_kernel<2>), dim3(2 * a.B), dim3(192), 0, st, a); break;
-    case 3: hipLaunchKernelGGL((ctc_lin_kernel<3>), dim3(2 * a.B), dim3(192), 0, st, a); break;
-    case 4: hipLaunchKernelGGL((ctc_lin_kernel<4>), dim3(2 * a.B), dim3(192), 0, st, a); break;
-    default: launch_ab(a, st); break;
-  }
-  // the sequences a lattice flagged (sharp[b]) again, exactly; the others' workgroups exit at
+  launch_ab(a, st);
+  // the sequences ctc_ab_kernel flagged (sharp[b]) again, exactly; the others' workgroups exit at
   // once.  U <= 255 only (the pairs fit one wave, 4 per lane): a flagged sequence with a longer
   // target keeps the log-space result, whose fp32 drift at such sharpness is ~1e-3 .. 1e-2
   // relative in the gradient (tests/test_gpu_ctc.py::test_ctc_sharp_long_targets_keep_log_space)
@@ -1406,10 +1074,9 @@ static CtcArgs make_args(const void* x, int is_logits, int B, int T, int V, int6
   a.S = 2 * umax + 1;
   a.Sp = 64 * states_per_lane(a.S);
   a.Umax = umax;
-  // steps per re-centring / 2 (the gradient's offset index): the one-wave lattices re-centre
-  // every kAb1R steps, the multi-wave one at every second halo exchange
-  a.lin = lin_ppl(umax) > 0;
-  a.kh = a.lin ? kAb1R / 2 : ab_halo_k(umax);
+  // steps per re-centring / 2 (the gradient's offset index): ctc_ab_kernel re-centres at every
+  // second halo exchange
+  a.kh = ab_halo_k(umax);
   a.blank = blank;
   a.sb = sb;
   a.stt = st;

@@ -1307,15 +1307,10 @@ bool fwd_split() {
   const char* e = getenv("SC_MLSTM_SPLIT");
   return !(e && e[0] == '0');
 }
-// SC_MLSTM_XCD=0 (environment, read per launch) keeps the plain (column block, bh) grid (A/B)
-bool fwd_xcd() {
-  const char* e = getenv("SC_MLSTM_XCD");
-  return !(e && e[0] == '0');
-}
 template <int DT, int IO, int DQ, int DV>
 void launch_fwd(const MArgs& a0, hipStream_t st) {
   MArgs a = a0;
-  a.xcd = (a.BH % 8 == 0 && fwd_xcd()) ? 1 : 0;
+  a.xcd = a.BH % 8 == 0;
   const dim3 grid = a.xcd ? dim3((DV / kCB) * a.BH) : dim3(DV / kCB, a.BH);
   if (!fwd_split()) {
     hipLaunchKernelGGL((mlstm_fw_walk<DT, IO, DQ, DV, 0>), grid, dim3(256), 0, st, a);

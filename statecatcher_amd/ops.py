@@ -223,10 +223,11 @@ def wgrad_splitk(dy, x, blocked_d=0):
     return colsum(part.view(S, N * K), perm).view(N, K)
 
 
-def wgrad_mfma_slabs(dy, x):
-    """The split-L MFMA weight-gradient kernel alone (sc_gemm_wgrad_bf16: gemm.hip) on the
-    current stream: fp32 slabs [S, N, K] whose fixed-order sum is dW = dy^T x, or None when the
-    shape is outside the kernel's tiling."""
+def wgrad_mfma(dy, x, blocked_d=0):
+    """dW = dy^T x in fp32 on the MFMA split-L kernel (sc_gemm_wgrad_bf16: gemm.hip), whose fp32
+    slabs [S, N, K] the fixed-order sum (sc_colsum) adds up, un-permuting step-blocked rows when
+    blocked_d = D; or None when the shape is outside the kernel's tiling (the caller uses the
+    library GEMM)."""
     M, N = dy.shape
     K = x.shape[1]
     lib = _lib.load()
@@ -238,40 +239,8 @@ def wgrad_mfma_slabs(dy, x):
     rc = lib.sc_gemm_wgrad_bf16(ptr(dy), dy.stride(0), ptr(x), x.stride(0), ptr(part), M, N, K, S,
                                 stream_of(dy))
     check(rc, "sc_gemm_wgrad_bf16")
-    return part
-
-
-def wgrad_slab_sum(part, blocked_d=0):
-    """dW [N, K] from wgrad_mfma_slabs' slabs: fixed-order sum (sc_colsum), un-permuting
-    step-blocked rows when blocked_d = D."""
-    S, N, K = part.shape
     perm = (blocked_d // 64, 7) if blocked_d else (1, 1)
     return colsum(part.view(S, N * K), perm).view(N, K)
-
-
-def wgrad_mfma(dy, x, blocked_d=0):
-    """dW = dy^T x in fp32 on the MFMA split-L kernel (sc_gemm_wgrad_bf16: gemm.hip) plus the
-    fixed-order slab sum (sc_colsum, which also un-permutes step-blocked rows), or None when the
-    shape is outside the kernel's tiling (the caller uses the library GEMM)."""
-    part = wgrad_mfma_slabs(dy, x)
-    return None if part is None else wgrad_slab_sum(part, blocked_d)
-
-
-# SC_WGRAD_STREAM=1 (A/B only): a cell's weight-gradient kernel on a side stream beside the
-# input-gradient GEMM, whose 376 tiles of 256 x 256 fill 1.5 waves of the 256 CUs, so that the
-# weight gradient's workgroups take the CUs its last wave leaves idle (slab sum and everything
-# after on the main stream; bitwise the same results).  Measured slower at C2 (5.13 vs 5.04 ms
-# per step): the persistent weight-gradient workgroups, started piecemeal, lose the per-XCD L2
-# sharing of their L-split (268 vs 165 us) and the library GEMM gets no faster.  Default off.
-USE_WGRAD_STREAM = os.environ.get("SC_WGRAD_STREAM", "0") == "1"
-_SIDE_STREAMS = {}
-
-
-def _side_stream(dev):
-    s = _SIDE_STREAMS.get(dev)
-    if s is None:
-        s = _SIDE_STREAMS[dev] = torch.cuda.Stream(device=dev)
-    return s
 
 
 # SC_WGRAD128=1: layer 0's weight gradient on the MFMA kernel's 128-column tile over a
@@ -279,25 +248,17 @@ def _side_stream(dev):
 # 2.6e-3).  Opt-in: same-box A/B 5.200-5.265 ms/step on vs 5.178-5.192 off (profiles/r6f_wgrad128_ab.md)
 USE_WGRAD128 = os.environ.get("SC_WGRAD128", "0") != "0"
 
-# SC_TN=0 routes the projection GEMMs back to the library (A/B timing in tools/ only)
-USE_TN = os.environ.get("SC_TN", "1") != "0"
-
 
 def tn_ok(a, b):
     """True when C = a b^T runs on the hand-written MFMA kernel (sc_gemm_tn_bf16): bf16 ROCm
     operands, K-contiguous, K % 64 == 0, N % 256 == 0, 16-byte aligned rows."""
-    return (USE_TN and a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16
+    return (a.is_cuda and a.dtype == torch.bfloat16 and b.dtype == torch.bfloat16
             and a.dim() == 2 and b.dim() == 2 and a.shape[1] == b.shape[1]
             and a.shape[1] % 64 == 0 and b.shape[0] % 256 == 0 and a.shape[0] > 0
             and a.stride(1) == 1 and b.stride(1) == 1 and a.stride(0) % 8 == 0
             and b.stride(0) % 8 == 0 and a.data_ptr() % 16 == 0 and b.data_ptr() % 16 == 0
             and (a.shape[0] + 256) * max(a.stride(0), b.shape[0]) * 2 < 2 ** 32
             and b.shape[0] * b.stride(0) * 2 < 2 ** 32)
-
-
-# SC_TN_FWD=<tile_m>: the K = 512 forward projections on sc_gemm_tn_bf16 with that tile code
-# (A/B of the hand-written kernels against the library in the step; default: the library)
-TN_FWD_TILE = int(os.environ.get("SC_TN_FWD", "-1"))
 
 
 def proj_fwd(x, w):
@@ -307,8 +268,6 @@ def proj_fwd(x, w):
     246 us; csrc/tn_gemm.hip header)."""
     if x.shape[1] <= 128 and tn_ok(x, w):
         return gemm_tn(x, w, 256)   # 256 x 256 four-phase kernel: 114 us vs 120 (192-row tiles)
-    if TN_FWD_TILE >= 0 and tn_ok(x, w):
-        return gemm_tn(x, w, TN_FWD_TILE)
     return torch.matmul(x, w.t())
 
 
@@ -440,7 +399,7 @@ def cell_image_spec(w, cdt, needs_dx):
         return None
     Din = w.shape[1]
     kp = Din + (-Din) % 64
-    tn = USE_TN and (7 * D) % 256 == 0
+    tn = (7 * D) % 256 == 0
     return (w, D, kp if tn else Din, needs_dx)
 
 
@@ -453,6 +412,19 @@ def step_blocked_rows(w, D, inverse=False, dtype=None):
     out = torch.empty((v.shape[1], v.shape[0], 64, K), dtype=dtype or w.dtype, device=w.device)
     out.copy_(v.transpose(0, 1))
     return out.view(7 * D, K)
+
+
+def _join_dh_last(dout, dh_last, gates):
+    """h_last is out[:, -1]: its gradient joins dout's last step (a copy; dout may be None)."""
+    if dh_last is None:
+        return dout
+    if dout is None:
+        B, T = gates.shape[:2]
+        dout = torch.zeros(B, T, dh_last.shape[-1], dtype=gates.dtype, device=gates.device)
+    else:
+        dout = dout.clone()
+    dout[:, -1] += dh_last.to(dout.dtype)
+    return dout
 
 
 class LucyCellFn(torch.autograd.Function):
@@ -480,7 +452,7 @@ class LucyCellFn(torch.autograd.Function):
         # layer 0 (Din = 80): the bf16 cast writes zero columns up to a multiple of 64, the
         # MFMA kernel's K stage (the weight gets the same zero columns)
         kp = Din + (-Din) % 64
-        tn = USE_TN and x2d.is_cuda and cdt == torch.bfloat16 and (7 * D) % 256 == 0
+        tn = x2d.is_cuda and cdt == torch.bfloat16 and (7 * D) % 256 == 0
         # the forward GEMM's copy of x with zero columns up to kp; the weight gradient keeps the
         # unpadded xc (its GEMM would otherwise sum 48 extra zero columns)
         if tn and kp != Din and x2d.dtype == torch.float32 and x2d.stride(1) == 1:
@@ -530,45 +502,18 @@ class LucyCellFn(torch.autograd.Function):
     def backward(ctx, dout, ds_last, dh_last):
         xc, wc, wt, gates, ckpt, bias = ctx.saved_tensors
         xdt, wdt, hdt, sdt = ctx.dtypes
-        if dh_last is not None:   # h_last is out[:, -1]: its gradient joins dout's last step
-            B, T = gates.shape[:2]
-            if dout is None:
-                dout = torch.zeros(B, T, dh_last.shape[-1], dtype=gates.dtype, device=gates.device)
-            else:
-                dout = dout.clone()
-            dout[:, -1] += dh_last.to(dout.dtype)
+        dout = _join_dh_last(dout, dh_last, gates)
         dgates, dh0, ds0, dbias = _scan_bwd(gates, ckpt, dout, ds_last, ctx.needs_input_grad[2],
                                             bias)
         dg2 = dgates.view(xc.shape[0], -1)
         bd = (dg2.shape[1] // 7) if ctx.blocked else 0
-        # the weight gradient's MFMA kernel on the side stream, beside the input gradient
-        part = None
-        if (USE_WGRAD_STREAM and ctx.needs_input_grad[0] and ctx.needs_input_grad[1]
-                and dg2.is_cuda and dg2.dtype == torch.bfloat16 and xc.dtype == torch.bfloat16):
-            main = torch.cuda.current_stream(dg2.device)
-            side = _side_stream(dg2.device)
-            side.wait_stream(main)   # dgates and x are complete
-            with torch.cuda.stream(side):
-                with _timed("gate_gemm_wgrad", dg2, 0):
-                    part = wgrad_mfma_slabs(dg2, xc)
-            if part is not None:
-                # (allocator: their blocks are not reused before the side stream's reads end)
-                dg2.record_stream(side)
-                xc.record_stream(side)
         dx = None
         if ctx.needs_input_grad[0]:
             with _timed("gate_gemm_dgrad", dg2, 0):
                 dx = torch.matmul(dg2, wt.t()) if wt is not None else proj_dgrad(dg2, wc)
             dx = dx.to(xdt)
         dw = None
-        if part is not None:
-            main.wait_stream(side)
-            part.record_stream(main)
-            dw = wgrad_slab_sum(part, bd)
-            if dw.shape[1] != ctx.din:   # (the zero-padded columns of layer 0's copy)
-                dw = dw[:, :ctx.din].contiguous()
-            dw = dw.to(wdt)
-        elif ctx.needs_input_grad[1]:
+        if ctx.needs_input_grad[1]:
             with _timed("gate_gemm_wgrad", dg2, 0):
                 dw = wgrad_splitk(dg2, xc, blocked_d=bd)
             if dw.shape[1] != ctx.din:   # (the zero-padded columns of layer 0's copy)
@@ -744,13 +689,7 @@ class LucyCellLNFn(torch.autograd.Function):
     def backward(ctx, dout, ds_last, dh_last):
         h2d, wt, gates, ckpt, bprime, rowsum, stat, w, gamma, beta = ctx.saved_tensors
         xdt, wdt, hdt, sdt, gdt, bdt = ctx.dtypes
-        if dh_last is not None:   # h_last is out[:, -1]: its gradient joins dout's last step
-            B, T = gates.shape[:2]
-            if dout is None:
-                dout = torch.zeros(B, T, dh_last.shape[-1], dtype=gates.dtype, device=gates.device)
-            else:
-                dout = dout.clone()
-            dout[:, -1] += dh_last.to(dout.dtype)
+        dout = _join_dh_last(dout, dh_last, gates)
         need_w = any(ctx.needs_input_grad[1:5])
         dgates, dh0, ds0, dbias = _scan_bwd(gates, ckpt, dout, ds_last, need_w, bprime,
                                             ln=(rowsum, stat))

@@ -53,12 +53,6 @@ for (L, I, J, blk) in [(48000, 3584, 512, 512), (48000, 1024, 512, 0)][:1 if QUI
 
     t_k = timeit(kern_only)
     t_m = timeit(lambda i: ops.wgrad_mfma(dys[i % R], xs[i % R], blk))
-    os.environ["SC_NO_MFMA_WGRAD"] = "1"
-
-    def lib_path(i):
-        M, N = dys[i % R].shape
-        return ops.wgrad_splitk.__wrapped__(dys[i % R], xs[i % R], blk) \
-            if hasattr(ops.wgrad_splitk, "__wrapped__") else None
 
     # the hipBLASLt formulation wgrad_splitk used before the MFMA kernel (S=16 batched + sum)
     def blas(i):
