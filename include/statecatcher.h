@@ -466,6 +466,58 @@ typedef struct sc_frame_cell_job {
 } sc_frame_cell_job;
 int sc_lucy_frame_cellb_multi(float eps, const sc_frame_cell_job* jobs, int njobs, void* stream);
 
+/*
+ * One streaming frame of one LucyRNNtriton layer (lucyrnn_triton.py:27-75 at T = 1) for B streams
+ * in ONE launch (csrc/lucy_frame.hip): g = x~ W^T + bias with W [7D][ldw] (fp32 or bf16), gate
+ * planes r z k v h_pre decay alpha, x~ = x [B][ldx] over K columns or, when ln_w is given,
+ * LayerNorm(x; ln_w, ln_b, eps) from the nst_in (n, mean, M2, -) records st_in [nst_in][B] that
+ * the previous layer's launch wrote (the inter-layer nn.LayerNorm); then per (row b, unit d), in
+ * fp32 with eps' = 1e-6 (lucyrnn_triton.py:214-242, the offline scan's arithmetic):
+ *   rc = sqrt((r^2 + z^2)/2 + eps')   rkv = sqrt((k^2 + v^2)/2 + eps')
+ *   z' = sigmoid(z / rc)   decay' = sigmoid(decay / sqrt(decay^2 + eps'))
+ *   alpha' = sigmoid(alpha / sqrt(alpha^2 + eps'))   kv = (k/rkv)(v/rkv) / (rkv^2 + eps')
+ *   s' = decay' s + alpha' kv   c = tanh(h_pre / sqrt(h_pre^2 + eps') + s')   h' = (1 - z') c + z' h
+ * With fp32 weights the projection sums k in ascending order (two K slices, each one chain of
+ * fp32 fmas): the rounding of a plain sgemm, which the reference module's goldens need.
+ * h, s: fp32 [B][D] state, updated in place (rows with mask[b] == 0 keep both; mask fp32 [B] or
+ * null).  out[b*ldo + d] = the new (or kept) h; st_out [D/16][B] float4 receives one record of
+ * out per 16 units and row for the next layer's prologue, or is null (last layer).
+ * D % 16 == 0; K % 4 == 0 (bf16 weights: % 8), K <= 2048; x, w, ln_w, ln_b 16-byte aligned with
+ * ldx % 4 == 0, ldw % 8 == 0, both >= K; ln_w, ln_b and st_in together or not at all.  B == 0 is
+ * a no-op.  No allocation, no atomics: captures into a HIP graph.
+ *
+ * sc_lucy_tframe_layer_multi: up to 8 such jobs in one launch (blockIdx.z = job), sharing w_dtype
+ * and eps; jobs with and without the prologue may mix (layer 0 has none).  A block of F frames of
+ * an L-layer model is then F + L - 1 launches: stage tau = layer l of frame tau - l for every l.
+ * Within a launch the jobs run concurrently, so the caller double-buffers each layer's out /
+ * st_out (the job of layer l - 1 writes frame j + 1 while layer l reads frame j).
+ */
+int sc_lucy_tframe_layer(const float* x, int64_t ldx, int K, const float* ln_w, const float* ln_b,
+                         const void* st_in, int nst_in, float eps, const void* w, int w_dtype,
+                         int64_t ldw, const float* bias, int B, int D, float* h, float* s,
+                         float* out, int64_t ldo, void* st_out, const float* mask, void* stream);
+typedef struct sc_tframe_job {
+  const float* x;
+  int64_t ldx;
+  int K;
+  const float* ln_w;
+  const float* ln_b;
+  const void* st_in;
+  int nst_in;
+  const void* w;
+  int64_t ldw;
+  const float* bias;
+  int B, D;
+  float* h;
+  float* s;
+  float* out;
+  int64_t ldo;
+  void* st_out;
+  const float* mask;
+} sc_tframe_job;
+int sc_lucy_tframe_layer_multi(int w_dtype, float eps, const sc_tframe_job* jobs, int njobs,
+                               void* stream);
+
 /* ---------------------------------------------------------------- column sums ----------- */
 
 /*

@@ -13,7 +13,7 @@ from .model import (ASRModel, CTCLoss, RNNTCompactPredictorJoiner, RNNTLoss, RNN
 from .ops import (ctc_greedy_decode, ctc_loss, ctc_nll, decay_scan, lucy_scan, mlstm_chunkwise,
                   rnnt_greedy_decode, rnnt_loss)
 from .decoder import ctc_greedy_decoder, rnnt_greedy_decoder
-from .streaming import StreamingLucyRNN
+from .streaming import StreamingLucyRNN, StreamingLucyRNNtriton
 from .frontend import make_frontend
 
 __all__ = [
@@ -21,5 +21,5 @@ __all__ = [
     "compute_loss", "detach_states", "build_lucyrnn_config", "build_xlstm_config", "ctc_greedy_decode", "ctc_loss", "ctc_nll", "decay_scan",
     "lucy_scan", "ctc_greedy_decoder", "rnnt_loss", "RNNTLoss", "RNNTPredictorJoiner",
     "RNNTCompactPredictorJoiner", "xLSTMLarge", "xLSTMLargeConfig", "mlstm_chunkwise",
-    "StreamingLucyRNN", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
+    "StreamingLucyRNN", "StreamingLucyRNNtriton", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
 ]

@@ -84,6 +84,9 @@ _SIGS = {
                                    _fp, _fp, _i64, _fp, _i32, _i32, _vp]),
     "sc_lucy_frame_gemm_multi": (_i32, [_i32, _i32, _c.c_float, _vp, _i32, _vp]),
     "sc_lucy_frame_cellb_multi": (_i32, [_c.c_float, _vp, _i32, _vp]),
+    "sc_lucy_tframe_layer": (_i32, [_fp, _i64, _i32, _fp, _fp, _vp, _i32, _c.c_float, _vp, _i32,
+                                    _i64, _fp, _i32, _i32, _fp, _fp, _fp, _i64, _vp, _fp, _vp]),
+    "sc_lucy_tframe_layer_multi": (_i32, [_i32, _c.c_float, _vp, _i32, _vp]),
     "sc_ctc_greedy_frames": (_i32, [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _fp, _i64, _i32, _vp,
                                     _vp, _i64, _i64, _vp]),
     "sc_mlstm_supported": (_i32, [_i32, _i32, _i32]),
@@ -169,6 +172,14 @@ class FrameCellJob(ctypes.Structure):
     _fields_ = [("z", _vp), ("st_z", _vp), ("nst_z", _i32), ("hp", _vp), ("st_h", _vp),
                 ("nst_h", _i32), ("lnz_w", _vp), ("lnz_b", _vp), ("lnh_w", _vp), ("lnh_b", _vp),
                 ("h", _vp), ("out", _vp), ("ldo", _i64), ("mask", _vp), ("B", _i32), ("D", _i32)]
+
+
+class TFrameJob(ctypes.Structure):
+    """sc_tframe_job (include/statecatcher.h)."""
+    _fields_ = [("x", _vp), ("ldx", _i64), ("K", _i32), ("ln_w", _vp), ("ln_b", _vp),
+                ("st_in", _vp), ("nst_in", _i32), ("w", _vp), ("ldw", _i64), ("bias", _vp),
+                ("B", _i32), ("D", _i32), ("h", _vp), ("s", _vp), ("out", _vp), ("ldo", _i64),
+                ("st_out", _vp), ("mask", _vp)]
 
 
 _LIB = None

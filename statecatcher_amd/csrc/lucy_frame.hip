@@ -27,13 +27,21 @@
 // the reference's arithmetic), v_mfma_f32_16x16x32_bf16 for bf16 weights (activations rounded to
 // bf16 on load, fp32 accumulate); a workgroup holds NT tiles x KS K-slices, summed through LDS.
 // Activations between kernels are fp32.
+//
+// The LucyRNNtriton layer (lucyrnn_triton.py:27-75, the model the training step runs) streams on
+// the same GEMM body with the FR_CELL_T epilogue: its normalisers are per element, so the whole
+// cell is the epilogue of the 7-gate projection, and the inter-layer nn.LayerNorm is the
+// PRO_LN prologue fed by the records the previous layer's epilogue wrote.  One launch per layer
+// and frame (sc_lucy_tframe_layer / _multi; statecatcher_amd/streaming.py StreamingLucyRNNtriton).
 #include "sc_common.h"
 
 #include <algorithm>
 
 namespace sc {
 
-enum { FR_PLAIN = 0, FR_STATS = 1, FR_CELL_UNFUSED = 2, FR_CELL_FUSED = 3 };
+enum { FR_PLAIN = 0, FR_STATS = 1, FR_CELL_UNFUSED = 2, FR_CELL_FUSED = 3,
+       FR_CELL_T = 4 };   // (4: the LucyRNNtriton layer, sc_lucy_tframe_layer only)
+constexpr bool is_cell(int epi) { return epi >= FR_CELL_UNFUSED; }
 
 struct FrameGemmArgs {
   const float* x;        // [B][ldx] fp32 activations (the A operand, before the prologue)
@@ -50,10 +58,12 @@ struct FrameGemmArgs {
   int B, N;
   int gstride;           // EPI_CELL: W row of gate g, unit d = g * gstride + d (gstride = D)
   // outputs
-  float* y;              // PLAIN / STATS: [B][ldy]; CELL: y (unfused) or hp (fused) [B][D]
+  float* y;              // PLAIN / STATS: [B][ldy]; CELL: y (unfused) or hp (fused) [B][D];
+                         // CELL_T: the layer's output [B][ldy]
   int64_t ldy;
-  float4* st_out;        // STATS: [ceil(N / 32)][B]; CELL: [D / 16][B] records of y/hp (fused)
-  float* z;              // CELL: raw z [B][D]
+  float4* st_out;        // STATS: [ceil(N / 32)][B]; CELL: [D / 16][B] records of y/hp (fused);
+                         // CELL_T: [D / 16][B] records of the output, or NULL
+  float* z;              // CELL: raw z [B][D]; CELL_T: fp32 state h [B][D], in place
   float4* st_z;          // CELL: [D / 16][B] records of z
   float* s;              // CELL: fp32 state [B][D], in place
   const float* mask;     // CELL: [B] or NULL
@@ -132,7 +142,11 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // (wave-uniform: scalar)
   const int t = w % NT, ks = w / NT;
   const int r0 = by * 16;
-  constexpr bool CELL = EPI == FR_CELL_UNFUSED || EPI == FR_CELL_FUSED;
+  constexpr bool CELL = is_cell(EPI);
+  constexpr bool TCELL = EPI == FR_CELL_T;
+  // CELL_T: the jobs of one launch are different layers, layer 0 without the LayerNorm prologue,
+  // so there it is a (workgroup-uniform) run-time property of the job
+  const bool ln = TCELL ? a.ln_w != nullptr : LN;
   constexpr int KSTEP = BF16W ? 32 : 16;
   const int cbase = CELL ? bx * 16 + t * a.gstride : (bx * NT + t) * 16;
   const int nsteps = (a.K + KSTEP - 1) / KSTEP;
@@ -152,6 +166,14 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
   bf16x8 wh[BF16W ? SMAXB : 1];
   const float* wrf = (const float*)a.w + (int64_t)(cok ? col : 0) * a.ldw;
   const __bf16* wrh = (const __bf16*)a.w + (int64_t)(cok ? col : 0) * a.ldw;
+  // CELL_T with fp32 weights sums each K slice in ascending k on ONE accumulator, the order of a
+  // plain fp32 dot product (what a BLAS sgemm and so the reference module compute): MFMA j of a
+  // step covers k0 + 4 j .. k0 + 4 j + 3, lane group q holding k0 + 4 j + q: the A rows are stored
+  // 4 x 4 transposed per 16 columns, and a step's weight pieces (loaded 16 bytes per lane as
+  // ever) are transposed across the four lane groups through the wave's own slot of part.  At the
+  // reference init a layer-0 gate can sit within rounding of 0, where x / sqrt(x^2 + 1e-6)
+  // amplifies a different summation order ~1e3x (tests/test_gpu_streaming_triton.py).
+  constexpr bool KORD = TCELL && !BF16W;
   auto load_chunk = [&](int c0) __attribute__((always_inline)) {
     if constexpr (!BF16W) {
 #pragma unroll
@@ -166,14 +188,16 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
   };
   load_chunk(sb);
   // epilogue operands
-  float e_bias[5] = {0.f, 0.f, 0.f, 0.f, 0.f}, e_s = 0.f, e_m = 1.f;
+  constexpr int NGATE = TCELL ? 7 : EPI == FR_CELL_FUSED ? 5 : 4;
+  float e_bias[TCELL ? 7 : 5] = {}, e_s = 0.f, e_m = 1.f, e_h = 0.f;
   {
     if constexpr (CELL) {
       if (w < 4) {
         const int rr = 4 * w + q, rc = min(r0 + rr, a.B - 1), d = bx * 16 + (lane & 15);
 #pragma unroll
-        for (int g = 0; g < (EPI == FR_CELL_FUSED ? 5 : 4); ++g) e_bias[g] = a.bias[g * a.gstride + d];
+        for (int g = 0; g < NGATE; ++g) e_bias[g] = a.bias[g * a.gstride + d];
         e_s = a.s[(int64_t)rc * a.gstride + d];
+        if constexpr (TCELL) e_h = a.z[(int64_t)rc * a.gstride + d];
         if (a.mask) e_m = a.mask[rc];
       }
     } else {
@@ -187,22 +211,25 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
   {
     const int per_row = kpad / 4;   // float4 pieces per row
     const int npc = 16 * per_row;
-    for (int i0 = 0; i0 < npc; i0 += 4 * NTH) {
-      float4 v[4], lw[4], lb[4];
+    // (CELL_T: 3 pieces -- 896 threads cover K = 512 in one pass, and the registers stay within
+    // the 128 a 14-wave workgroup may use)
+    constexpr int NPC = TCELL ? 3 : 4;
+    for (int i0 = 0; i0 < npc; i0 += NPC * NTH) {
+      float4 v[NPC], lw[NPC], lb[NPC];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < NPC; ++j) {
         const int i = i0 + j * NTH + threadIdx.x;
         const int rr = i / per_row, k = 4 * (i % per_row), r = r0 + rr;
         v[j] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (i < npc && r < a.B && k < a.K) {   // (K % 4 == 0: a piece is wholly in or out)
           v[j] = *(const float4*)(a.x + (int64_t)r * a.ldx + k);
-          if (LN) {
+          if (ln) {
             lw[j] = *(const float4*)(a.ln_w + k);
             lb[j] = *(const float4*)(a.ln_b + k);
           }
         }
       }
-      if (LN && i0 == 0) {   // the row statistics, once per workgroup, while the pieces load
+      if (ln && i0 == 0) {   // the row statistics, once per workgroup, while the pieces load
         if (a.nst_in <= 64) {   // wave w: rows w, w + nwaves, ...; one record per lane
           for (int rr = w; rr < 16; rr += NT * KS) {
             const float2 st = row_stats_wave(a.st_in + min(r0 + rr, a.B - 1), a.nst_in, a.B,
@@ -222,18 +249,26 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
         __syncthreads();
       }
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
+      for (int j = 0; j < NPC; ++j) {
         const int i = i0 + j * NTH + threadIdx.x;
         const int rr = i / per_row, k = 4 * (i % per_row), r = r0 + rr;
         if (i < npc) {
-          if (LN && r < a.B && k < a.K) {
+          if (ln && r < a.B && k < a.K) {
             const float mu = stat[rr][0], rs = stat[rr][1];
             v[j].x = (v[j].x - mu) * rs * lw[j].x + lb[j].x;
             v[j].y = (v[j].y - mu) * rs * lw[j].y + lb[j].y;
             v[j].z = (v[j].z - mu) * rs * lw[j].z + lb[j].z;
             v[j].w = (v[j].w - mu) * rs * lw[j].w + lb[j].w;
           }
-          *(float4*)(xs + rr * kpitch + k) = v[j];
+          if constexpr (KORD) {   // column 16 s + 4 c + e -> slot 16 s + 4 e + c
+            float* p = xs + rr * kpitch + (k & ~15) + ((k >> 2) & 3);
+            p[0] = v[j].x;
+            p[4] = v[j].y;
+            p[8] = v[j].z;
+            p[12] = v[j].w;
+          } else {
+            *(float4*)(xs + rr * kpitch + k) = v[j];
+          }
         }
       }
     }
@@ -253,12 +288,29 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
       __builtin_amdgcn_sched_barrier(0);   // keep the loads ahead of the MFMAs (no sinking)
 #pragma unroll
       for (int i = 0; i < SMAXF; ++i) {
-        const bool in = c0 + i < se && (c0 + i) * 16 + 4 * q < a.K;
+        // (KORD: the transposed rows already hold 0 in every column past K)
+        const bool in = c0 + i < se && (KORD || (c0 + i) * 16 + 4 * q < a.K);
         float4 xa = xb[i];
         xa.x = in ? xa.x : 0.f;
         xa.y = in ? xa.y : 0.f;
         xa.z = in ? xa.z : 0.f;
         xa.w = in ? xa.w : 0.f;
+        if constexpr (KORD) {   // k ascending on one accumulator
+          // lane (c, j) holds W[c][k0 + 4 j + e] in element e: lane (c, q) takes element q of
+          // lane (c, j) for MFMA j (wave-private LDS, in order: no barrier; reads conflict-free)
+          float* tw = &part[w][0][0];
+          tw[4 * lane + 0] = wf[i].x;
+          tw[4 * lane + 1] = wf[i].y;
+          tw[4 * lane + 2] = wf[i].z;
+          tw[4 * lane + 3] = wf[i].w;
+          const int rd = 4 * (lane & 15) + q;
+          const float w0 = tw[rd], w1 = tw[rd + 64], w2 = tw[rd + 128], w3 = tw[rd + 192];
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.x, w0, acc0, 0, 0, 0);
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.y, w1, acc0, 0, 0, 0);
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.z, w2, acc0, 0, 0, 0);
+          acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.w, w3, acc0, 0, 0, 0);
+          continue;
+        }
         // k slot q of MFMA j is k0 + j for both operands: the sum runs over the same k set
         acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.x, wf[i].x, acc0, 0, 0, 0);
         acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa.y, wf[i].y, acc1, 0, 0, 0);
@@ -332,6 +384,39 @@ __device__ __forceinline__ void frame_gemm_body(const FrameGemmArgs& a, const in
         if (r0 + rr < a.B) a.st_out[(int64_t)bx * a.B + r0 + rr] = make_float4(r.x, r.y, r.z, 0.0f);
       }
     }
+  } else if constexpr (TCELL) {
+    // The whole LucyRNNtriton cell (lucyrnn_triton.py:214-242, the arithmetic of lucy_scan.hip's
+    // step_terms: every normaliser is per element) for the 16 x 16 (row, unit) elements, one per
+    // lane of waves 0..3; gate planes r z k v h_pre decay alpha.  h and s are read (above) and
+    // written by the one lane owning the element.
+    if (w < 4) {
+      const int rr = 4 * w + q, r = r0 + rr, d = bx * 16 + (lane & 15);
+      const int D = a.gstride;
+      auto gate = [&](int g) { return part[g][rr][lane & 15] + e_bias[g]; };
+      constexpr float kEpsT = 1e-6f;
+      const float gr = gate(0), gz = gate(1), gk = gate(2), gv = gate(3), ghp = gate(4);
+      const float gdc = gate(5), gal = gate(6);
+      const float rc2 = (gr * gr + gz * gz) * 0.5f + kEpsT;
+      const float qkv = (gk * gk + gv * gv) * 0.5f + kEpsT;   // rho_kv^2
+      const float zg = sigm(gz * rsq(rc2));
+      const float dec = sigm(gdc * rsq(gdc * gdc + kEpsT));
+      const float alp = sigm(gal * rsq(gal * gal + kEpsT));
+      const float hn = ghp * rsq(ghp * ghp + kEpsT);
+      const float iq = rsq(qkv);
+      const float kv = (gk * iq) * (gv * iq) * rcp(qkv + kEpsT);
+      const float sn = dec * e_s + alp * kv;
+      const float c = sigm(2.0f * (hn + sn)) * 2.0f - 1.0f;   // tanh as the offline scan has it
+      const float hv = (1.0f - zg) * c + zg * e_h;
+      const float m = e_m;
+      const float ho = m * hv + (1.0f - m) * e_h;
+      const float4 so = stats16(ho);
+      if (r < a.B) {
+        a.s[(int64_t)r * D + d] = m * sn + (1.0f - m) * e_s;
+        a.z[(int64_t)r * D + d] = ho;
+        a.y[(int64_t)r * a.ldy + d] = ho;
+        if (a.st_out && (lane & 15) == 0) a.st_out[(int64_t)bx * a.B + r] = so;
+      }
+    }
   } else {
     // the cell's elementwise part for the 16 x 16 (row, unit) elements: one per lane of wave 0..3
     if (w < 4) {
@@ -381,7 +466,7 @@ struct FrameGemmJobs {
 template <bool BF16W, bool LN, int EPI, int NT, int KS>
 __global__ void __launch_bounds__(64 * NT * KS, 4) lucy_frame_gemm_multi(FrameGemmJobs jobs) {
   const FrameGemmArgs& a = jobs.j[blockIdx.z];
-  constexpr bool CELL = EPI == FR_CELL_UNFUSED || EPI == FR_CELL_FUSED;
+  constexpr bool CELL = is_cell(EPI);
   const int nblk = CELL ? a.gstride / 16 : (a.N + 16 * NT - 1) / (16 * NT);
   if ((int)blockIdx.x >= nblk || (int)blockIdx.y * 16 >= a.B) return;
   frame_gemm_body<BF16W, LN, EPI, NT, KS>(a, blockIdx.x, blockIdx.y);
@@ -500,7 +585,7 @@ static void launch_gemm(const FrameGemmArgs& a, int nblk, hipStream_t st) {
 template <bool BF16W, bool LN, int EPI, int NT, int KS>
 static void launch_gemm_multi(const FrameGemmJobs& jobs, int nj, hipStream_t st) {
   const int kstep = BF16W ? 32 : 16;
-  constexpr bool CELL = EPI == FR_CELL_UNFUSED || EPI == FR_CELL_FUSED;
+  constexpr bool CELL = is_cell(EPI);
   size_t lds = 0;
   int gx = 1, gy = 1;
   for (int i = 0; i < nj; ++i) {
@@ -652,6 +737,86 @@ extern "C" int sc_lucy_frame_gemm_multi(int epi, int w_dtype, float eps,
     else dispatch_gemm_multi<false, false>(epi, fj, nj, st);
   }
   return launch_status("sc_lucy_frame_gemm_multi");
+}
+
+// ---- one streaming frame of one LucyRNNtriton layer: the FR_CELL_T epilogue ------------------
+// 7 gate tiles x 2 K-slices (896 threads): a workgroup owns 16 units of every gate for 16 rows, so
+// the cell is the projection's epilogue and a layer of a frame is ONE launch.  (2 K-slices as the
+// native gate GEMMs keep them; 14 waves at <= 128 VGPRs are one workgroup per CU.)
+static int tframe_check(const char* fn, int w_dtype, const float* x, int64_t ldx, int K,
+                        const float* ln_w, const float* ln_b, const void* st_in, int nst_in,
+                        const void* w, int64_t ldw, const float* bias, int B, int D, float* h,
+                        float* s, float* out) {
+  SC_REQUIRE(w_dtype == SC_F32 || w_dtype == SC_BF16, "%s: weights fp32 or bf16", fn);
+  SC_REQUIRE(B >= 0 && K > 0 && D > 0, "%s: bad shape B=%d K=%d D=%d", fn, B, K, D);
+  SC_REQUIRE(D % 16 == 0, "%s: D = %d must be a multiple of 16", fn, D);
+  if (B == 0) return 0;
+  SC_REQUIRE(x && w && bias && h && s && out, "%s: null pointer", fn);
+  SC_REQUIRE(K % 4 == 0 && ldx % 4 == 0 && ldw % 8 == 0 && ldx >= K && ldw >= K &&
+                 (uintptr_t)x % 16 == 0 && (uintptr_t)w % 16 == 0,
+             "%s: rows must be 16-byte aligned (ldx %% 4, ldw %% 8, K %% 4) and hold K", fn);
+  SC_REQUIRE(w_dtype == SC_F32 || K % 8 == 0, "%s: bf16 weights need K %% 8 == 0", fn);
+  SC_REQUIRE(K <= 2048, "%s: K = %d above 2048 (the A rows live in LDS)", fn, K);
+  SC_REQUIRE(!ln_w || ((uintptr_t)ln_w % 16 == 0 && (uintptr_t)ln_b % 16 == 0),
+             "%s: LayerNorm parameters must be 16-byte aligned", fn);
+  SC_REQUIRE((ln_w == nullptr) == (ln_b == nullptr) && (!ln_w || (st_in && nst_in > 0)),
+             "%s: LayerNorm prologue needs weight, bias and statistics", fn);
+  return 0;
+}
+
+static FrameGemmArgs tframe_args(const float* x, int64_t ldx, int K, const float* ln_w,
+                                 const float* ln_b, const void* st_in, int nst_in, float eps,
+                                 const void* w, int64_t ldw, const float* bias, int B, int D,
+                                 float* h, float* s, float* out, int64_t ldo, void* st_out,
+                                 const float* mask) {
+  FrameGemmArgs a;
+  a.x = x; a.ldx = ldx; a.K = K; a.ln_w = ln_w; a.ln_b = ln_b; a.st_in = (const float4*)st_in;
+  a.nst_in = nst_in; a.eps = eps; a.w = w; a.ldw = ldw; a.bias = bias; a.B = B; a.N = 7 * D;
+  a.gstride = D;
+  a.y = out; a.ldy = ldo; a.st_out = (float4*)st_out; a.z = h; a.st_z = nullptr; a.s = s;
+  a.mask = mask;
+  return a;
+}
+
+extern "C" int sc_lucy_tframe_layer(const float* x, int64_t ldx, int K, const float* ln_w,
+                                    const float* ln_b, const void* st_in, int nst_in, float eps,
+                                    const void* w, int w_dtype, int64_t ldw, const float* bias,
+                                    int B, int D, float* h, float* s, float* out, int64_t ldo,
+                                    void* st_out, const float* mask, void* stream) {
+  clear_error();
+  const int rc = tframe_check("sc_lucy_tframe_layer", w_dtype, x, ldx, K, ln_w, ln_b, st_in, nst_in,
+                              w, ldw, bias, B, D, h, s, out);
+  if (rc || B == 0) return rc;
+  const FrameGemmArgs a = tframe_args(x, ldx, K, ln_w, ln_b, st_in, nst_in, eps, w, ldw, bias, B, D,
+                                      h, s, out, ldo, st_out, mask);
+  hipStream_t st = (hipStream_t)stream;
+  if (w_dtype == SC_BF16) launch_gemm<true, true, FR_CELL_T, 7, 2>(a, D / 16, st);
+  else launch_gemm<false, true, FR_CELL_T, 7, 2>(a, D / 16, st);
+  return launch_status("sc_lucy_tframe_layer");
+}
+
+extern "C" int sc_lucy_tframe_layer_multi(int w_dtype, float eps, const sc_tframe_job* jobs,
+                                          int njobs, void* stream) {
+  clear_error();
+  SC_REQUIRE(njobs >= 0 && njobs <= kMaxFrameJobs && (njobs == 0 || jobs),
+             "sc_lucy_tframe_layer_multi: 0..%d jobs per call", kMaxFrameJobs);
+  FrameGemmJobs fj{};
+  int nj = 0;
+  for (int i = 0; i < njobs; ++i) {
+    const sc_tframe_job& j = jobs[i];
+    const int rc = tframe_check("sc_lucy_tframe_layer_multi", w_dtype, j.x, j.ldx, j.K, j.ln_w,
+                                j.ln_b, j.st_in, j.nst_in, j.w, j.ldw, j.bias, j.B, j.D, j.h, j.s,
+                                j.out);
+    if (rc) return rc;
+    if (j.B == 0) continue;
+    fj.j[nj++] = tframe_args(j.x, j.ldx, j.K, j.ln_w, j.ln_b, j.st_in, j.nst_in, eps, j.w, j.ldw,
+                             j.bias, j.B, j.D, j.h, j.s, j.out, j.ldo, j.st_out, j.mask);
+  }
+  if (nj == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  if (w_dtype == SC_BF16) launch_gemm_multi<true, true, FR_CELL_T, 7, 2>(fj, nj, st);
+  else launch_gemm_multi<false, true, FR_CELL_T, 7, 2>(fj, nj, st);
+  return launch_status("sc_lucy_tframe_layer_multi");
 }
 
 static int frame_cellb_check(const char* fn, const float* z, const void* st_z, int nst_z,

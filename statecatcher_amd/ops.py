@@ -1243,6 +1243,46 @@ def lucy_frame_cellb_multi(jobs, stream, eps=1e-5):
                                             len(part), stream), "sc_lucy_frame_cellb_multi")
 
 
+def lucy_tframe_layer(x, w, bias, h, s, out, st_out=None, ln=None, st_in=None, mask=None,
+                      eps=1e-5):
+    """One streaming frame of one LucyRNNtriton layer in one launch (csrc/lucy_frame.hip,
+    include/statecatcher.h sc_lucy_tframe_layer): x fp32 [B, K], w fp32/bf16 [7D, K], bias fp32
+    [7D]; h, s fp32 [B, D] in place; out fp32 [B, D] (row stride out.stride(0)) <- the new h;
+    st_out [D/16, B, 4] <- its statistics records, or None (last layer); ln = (weight, bias) of
+    the inter-layer LayerNorm over K with st_in the previous layer's records.  No allocation:
+    safe inside a hipGraph capture."""
+    B, K = x.shape
+    lw, lb = ln if ln is not None else (None, None)
+    rc = _lib.load().sc_lucy_tframe_layer(
+        ptr(x), x.stride(0), K, ptr(lw), ptr(lb), ptr(st_in),
+        st_in.shape[0] if st_in is not None else 0, float(eps), ptr(w), dtype_code(w), w.stride(0),
+        ptr(bias), B, h.shape[1], ptr(h), ptr(s), ptr(out), out.stride(0), ptr(st_out), ptr(mask),
+        stream_of(x))
+    check(rc, "sc_lucy_tframe_layer")
+
+
+def tframe_job(x, w, bias, h, s, out, st_out=None, ln=None, st_in=None, mask=None):
+    """One job of lucy_tframe_layer_multi (the arguments of one lucy_tframe_layer call)."""
+    B, K = x.shape
+    lw, lb = ln if ln is not None else (None, None)
+    return _lib.TFrameJob(ptr(x), x.stride(0), K, ptr(lw), ptr(lb), ptr(st_in),
+                          st_in.shape[0] if st_in is not None else 0, ptr(w), w.stride(0),
+                          ptr(bias), B, h.shape[1], ptr(h), ptr(s), ptr(out), out.stride(0),
+                          ptr(st_out), ptr(mask))
+
+
+def lucy_tframe_layer_multi(w_dtype, jobs, stream, eps=1e-5):
+    """Independent LucyRNNtriton layer frames (TFrameJob list, <= 8 per launch: longer lists take
+    ceil(n / 8) launches) -- sc_lucy_tframe_layer_multi.  The jobs of a launch run concurrently:
+    none may read what another writes.  No allocation: safe inside a hipGraph capture."""
+    lib = _lib.load()
+    code = dtype_code(torch.empty(0, dtype=w_dtype))
+    for k in range(0, len(jobs), 8):
+        part = jobs[k:k + 8]
+        check(lib.sc_lucy_tframe_layer_multi(code, float(eps), (_lib.TFrameJob * len(part))(*part),
+                                             len(part), stream), "sc_lucy_tframe_layer_multi")
+
+
 def ctc_greedy_frames(logits, prev, emit, mask=None, blank=0):
     """ctc_greedy_step over F frames in order, one launch (sc_ctc_greedy_frames): logits
     [F, B, V] (unit inner stride), prev int32 [B] contiguous, emit int32 [F, B], mask fp32

@@ -43,6 +43,12 @@ transducer decode instead (the reference has none): enc_p = joiner.enc_proj(logi
 block's K frames (lucy_frame_gemm on the frame engine, addmm on the library engine), then ONE
 sc_rnnt_greedy_decode launch (csrc/rnnt_decode.hip) with each stream's last emitted token carried
 in ``prev`` (``blank`` at stream start, compute_loss's predictor prefix), inside the same graph.
+
+StreamingLucyRNNtriton streams a LucyRNNtriton (lucyrnn_triton.py, the encoder the training step
+runs) the same way.  Its cell normalises per element, so a layer of a frame is ONE launch
+(lucy_tframe_layer: LayerNorm on load, 7-gate projection, cell in the epilogue), a frame L + 2
+launches and a wavefront block (K + L - 1) + 2.  Both classes share the block / capture / tail /
+API code (_StreamBase).
 """
 import torch
 
@@ -55,7 +61,154 @@ def _ln_params(mod, on):
         if on else None
 
 
-class StreamingLucyRNN:
+class _StreamBase:
+    """What the streaming decoders share: the block (frame by frame or as a wavefront), its
+    capture as a hipGraph, the greedy CTC / transducer tail, and step / decode / reset / state.
+    A subclass builds the static buffers (x, mask, h, s, logits, emit, prev, ...) and provides
+    _frame(j) and _block_wavefront()."""
+
+    joiner = False   # True on an instance built with a joiner: the block ends in the transducer decode
+
+    def _init_joiner(self, joiner, max_symbols, dev):
+        """Snapshot the joiner: enc_proj for the block's projection, the [V, J] predictor table
+        and the output projection for the decode (fp32 on the frame engine, whose activations
+        are fp32; ``dtype`` on the library engine), and the static decode outputs."""
+        from .decoder import rnnt_joiner_tables
+        jm = getattr(joiner, "module", joiner)
+        B, K, V = self.B, self.K, self.V
+        if jm.enc_proj.in_features != V or jm.joiner.out_features != V:
+            raise ValueError(f"joiner must project the model's {V} outputs and emit {V} tokens")
+        if not 1 <= int(max_symbols) <= 64:
+            raise ValueError("max_symbols must be in [1, 64]")
+        self.max_symbols, self.J = int(max_symbols), jm.enc_proj.out_features
+        frame = self.engine == "frame"
+        if frame and (V % 8 != 0 or V > 2048):
+            raise ValueError("engine='frame' with a joiner needs vocab_size % 8 == 0 and <= 2048 "
+                             "(enc_proj runs on lucy_frame_gemm); use engine='library'")
+        wdt = self.dtype
+        self.w_enc = jm.enc_proj.weight.detach().to(wdt).contiguous()
+        self.b_enc = jm.enc_proj.bias.detach().to(torch.float32 if frame else wdt).contiguous()
+        self.pred_tab, self.w_join, self.b_join = rnnt_joiner_tables(
+            jm, torch.float32 if frame else wdt)
+        cap = K * self.max_symbols
+        self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+        self.tok_frames = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
+        self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
+
+    def _rnnt_block(self):
+        """enc_proj over the block's K frames of logits, then one greedy transducer launch."""
+        K, B = self.K, self.B
+        lg, ep = self.logits.view(K * B, self.V), self.enc_p.view(K * B, self.J)
+        if self.engine == "frame":
+            ops.lucy_frame_gemm(ops.FRAME_PLAIN, lg, self.w_enc, self.b_enc, ep)
+        else:
+            torch.addmm(self.b_enc, lg, self.w_enc.t(), out=ep)
+        ops.rnnt_greedy_decode(self.enc_p.transpose(0, 1), self.pred_tab, self.w_join, self.b_join,
+                               mask=self.mask.t(), blank=self.blank, max_symbols=self.max_symbols,
+                               prev=self.prev, out=(self.tokens, self.counts, self.tok_frames))
+
+    def _block(self):
+        if self.schedule == "wavefront":
+            return self._block_wavefront()
+        for j in range(self.K):
+            self._frame(j)
+        if self.joiner:
+            self._rnnt_block()
+
+    def _capture(self):
+        side = torch.cuda.Stream(self.x.device)
+        side.wait_stream(torch.cuda.current_stream(self.x.device))
+        with torch.cuda.stream(side):   # warm-up: library workspaces, kernel loading
+            self._block()
+        torch.cuda.current_stream(self.x.device).wait_stream(side)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph):
+            self._block()
+
+    # ------------------------------------------------------------------------------- API ---
+    def reset(self, hidden_states=None, streams=None):
+        """Start streams afresh: state from ``hidden_states`` ((h list, s list) of [B,D], as the
+        reference's forward takes) or zero, prev token = none (``blank`` with a joiner).
+        ``streams``: index tensor/list of the streams to reset (default all)."""
+        idx = slice(None) if streams is None else torch.as_tensor(streams, device=self.x.device)
+        for l in range(self.L):
+            for buf, src in ((self.h[l], None if hidden_states is None else hidden_states[0][l]),
+                             (self.s[l], None if hidden_states is None else hidden_states[1][l])):
+                if src is None:
+                    buf[idx] = 0.0
+                else:
+                    buf[idx] = src.to(buf.device, torch.float32)[idx]
+        self.prev[idx] = self.blank if self.joiner else -1
+
+    def state(self):
+        """(h list, s list) fp32 copies — the reference's (h, s) return (lucyrnn.py:188-189)."""
+        return [t.clone() for t in self.h], [t.clone() for t in self.s]
+
+    def _x_in(self):
+        """The [K, B, Din] view of the static input buffer that step() fills."""
+        return self.x
+
+    def step(self, x, mask=None):
+        """Advance every stream by K = frames_per_call model frames.  x [B, K, input_dim *
+        stack_order] (already stacked); mask [B, K] (bool/float, None = all live).  Returns
+        emit int32 [B, K] on the device: the token decoder.py appends at that frame, or -1.
+        The logits of the block stay in ``self.logits`` ([K, B, V]).
+        With a joiner: returns (tokens int32 [B, K * max_symbols], frames, counts int32 [B]) on
+        the device instead: row b's first counts[b] tokens are this block's emissions, frames
+        their frame index within the block; later entries are stale."""
+        self._x_in().copy_(x.transpose(0, 1))
+        if mask is None:
+            self.mask.fill_(1.0)
+        else:
+            self.mask.copy_(mask.transpose(0, 1))
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self._block()
+        if self.joiner:
+            return self.tokens, self.tok_frames, self.counts
+        return self.emit.t()
+
+    def decode(self, feats, masks=None, return_logits=False):
+        """Whole utterances through the streaming path: feats [B, T, input_dim] raw frames,
+        stacked as the model does (lucyrnn.py:92-99: the tail T % stack_order is dropped, a
+        stacked frame is live when all its frames are).  Returns the decoder.py token lists
+        (and logits [B, T', V] if asked).  One host sync at the end."""
+        B, T, F = feats.shape
+        k = self.cfg.stack_order
+        Tt = T - T % k
+        x = feats[:, :Tt].reshape(B, Tt // k, F * k)
+        m = None
+        if masks is not None:
+            m = masks.reshape(B, -1)[:, :Tt].reshape(B, Tt // k, k).all(-1).float()
+        T2 = x.shape[1]
+        emits, logits = [], []
+        for t0 in range(0, T2, self.K):
+            n = min(self.K, T2 - t0)
+            xb = torch.zeros(B, self.K, x.shape[2], dtype=self.dtype, device=self.x.device)
+            xb[:, :n] = x[:, t0:t0 + n]
+            mb = torch.zeros(B, self.K, device=self.x.device)   # padding frames are masked out
+            mb[:, :n] = 1.0 if m is None else m[:, t0:t0 + n]
+            if self.joiner:
+                tk, _, ct = self.step(xb, mb)
+                emits.append(torch.cat([ct.unsqueeze(1), tk], 1))   # (a copy: count, tokens)
+            else:
+                emits.append(self.step(xb, mb)[:, :n].clone())
+            if return_logits:
+                logits.append(self.logits[:n].transpose(0, 1).clone())
+        em = torch.cat(emits, 1).cpu() if emits else torch.zeros(B, 0, dtype=torch.int32)
+        if self.joiner:
+            w = 1 + self.K * self.max_symbols
+            toks = [[t for k in range(0, em.shape[1], w) for t in row[k + 1:k + 1 + row[k]]]
+                    for row in em.tolist()]
+        else:
+            toks = [[int(t) for t in row if t >= 0] for row in em]
+        if return_logits:
+            return toks, torch.cat(logits, 1) if logits else None
+        return toks
+
+
+class StreamingLucyRNN(_StreamBase):
     """Decode ``batch`` concurrent streams through ``model`` (a native LucyRNN; its weights are
     snapshotted at construction) ``frames_per_call`` model frames per call.
 
@@ -64,8 +217,6 @@ class StreamingLucyRNN:
     joiner: decode as a transducer with this joiner (at most ``max_symbols`` tokens per frame)
     instead of greedy CTC; its weights are snapshotted too.
     """
-
-    joiner = False   # True on an instance built with a joiner: the block ends in the transducer decode
 
     def __init__(self, model: LucyRNN, batch: int, frames_per_call: int = 1,
                  dtype=torch.float32, blank: int = 0, graph: bool = True, engine: str = "auto",
@@ -167,44 +318,6 @@ class StreamingLucyRNN:
         if graph:
             self._capture()
         self.reset()
-
-    def _init_joiner(self, joiner, max_symbols, dev):
-        """Snapshot the joiner: enc_proj for the block's projection, the [V, J] predictor table
-        and the output projection for the decode (fp32 on the frame engine, whose activations
-        are fp32; ``dtype`` on the library engine), and the static decode outputs."""
-        from .decoder import rnnt_joiner_tables
-        jm = getattr(joiner, "module", joiner)
-        B, K, V = self.B, self.K, self.V
-        if jm.enc_proj.in_features != V or jm.joiner.out_features != V:
-            raise ValueError(f"joiner must project the model's {V} outputs and emit {V} tokens")
-        if not 1 <= int(max_symbols) <= 64:
-            raise ValueError("max_symbols must be in [1, 64]")
-        self.max_symbols, self.J = int(max_symbols), jm.enc_proj.out_features
-        frame = self.engine == "frame"
-        if frame and (V % 8 != 0 or V > 2048):
-            raise ValueError("engine='frame' with a joiner needs vocab_size % 8 == 0 and <= 2048 "
-                             "(enc_proj runs on lucy_frame_gemm); use engine='library'")
-        wdt = self.dtype
-        self.w_enc = jm.enc_proj.weight.detach().to(wdt).contiguous()
-        self.b_enc = jm.enc_proj.bias.detach().to(torch.float32 if frame else wdt).contiguous()
-        self.pred_tab, self.w_join, self.b_join = rnnt_joiner_tables(
-            jm, torch.float32 if frame else wdt)
-        cap = K * self.max_symbols
-        self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
-        self.tok_frames = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
-        self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
-
-    def _rnnt_block(self):
-        """enc_proj over the block's K frames of logits, then one greedy transducer launch."""
-        K, B = self.K, self.B
-        lg, ep = self.logits.view(K * B, self.V), self.enc_p.view(K * B, self.J)
-        if self.engine == "frame":
-            ops.lucy_frame_gemm(ops.FRAME_PLAIN, lg, self.w_enc, self.b_enc, ep)
-        else:
-            torch.addmm(self.b_enc, lg, self.w_enc.t(), out=ep)
-        ops.rnnt_greedy_decode(self.enc_p.transpose(0, 1), self.pred_tab, self.w_join, self.b_join,
-                               mask=self.mask.t(), blank=self.blank, max_symbols=self.max_symbols,
-                               prev=self.prev, out=(self.tokens, self.counts, self.tok_frames))
 
     # ------------------------------------------------------------------------------ frame --
     def _frame_fused_chain(self, j):
@@ -316,98 +429,148 @@ class StreamingLucyRNN:
             return self._rnnt_block()
         ops.ctc_greedy_frames(self.logits, self.prev, self.emit, mask=self.mask, blank=self.blank)
 
-    def _block(self):
-        if self.schedule == "wavefront":
-            return self._block_wavefront()
-        for j in range(self.K):
-            self._frame(j)
+
+class StreamingLucyRNNtriton(_StreamBase):
+    """Decode ``batch`` concurrent streams through a LucyRNNtriton (the model the training step
+    runs; weights snapshotted at construction) ``frames_per_call`` frames per call.
+
+    A layer of a frame is ONE launch (ops.lucy_tframe_layer, csrc/lucy_frame.hip): the inter-layer
+    LayerNorm applied on load from the previous layer's records, the 7-gate projection on MFMA
+    (fp32 or bf16 weights per ``dtype``; activations and state fp32), the cell in the epilogue,
+    h / s updated in place.  schedule="frame": L launches, the output projection and the greedy
+    step per frame.  schedule="wavefront" (default): stage tau runs layer l of frame tau - l for
+    every l as one multi-job launch, then one output projection over the block and one greedy /
+    transducer launch: (K + L - 1) + 2 launches per block.
+
+    The jobs of a stage run concurrently, and layer l - 1 (frame j + 1) writes what layer l
+    (frame j) reads, so each layer's output and records are double-buffered by the frame's parity
+    within the block: xo[l][j & 1] is written in stage l + j, read in stage l + j + 1, and next
+    written (frame j + 2) in stage l + j + 2.  The same buffers serve every block, so the block
+    is captured once.
+
+    reset() takes and state() returns LucyRNNtriton's own nesting ([[h] * L], [[s] * L])
+    ([track][layer] of fp32 [B, D]): ``model(x, st.state())`` and ``st.reset(model(x)[1])`` hand
+    over between an offline segment and the stream.  Multi-track models, hidden_dim not a
+    multiple of 16 or above 2048 are refused: use the offline forward with carried state there.
+    """
+
+    engine = "frame"   # (the transducer tail's enc_proj runs on lucy_frame_gemm)
+
+    def __init__(self, model, batch: int, frames_per_call: int = 1, dtype=torch.float32,
+                 blank: int = 0, graph: bool = True, schedule: str = "wavefront", joiner=None,
+                 max_symbols: int = 4):
+        from .lucyrnn_triton import LucyRNNtriton
+        alt = ("; use LucyRNNtriton.forward(x, hidden_states) on chunks with carried state "
+               "instead")
+        if not isinstance(model, LucyRNNtriton):
+            raise TypeError("StreamingLucyRNNtriton streams a LucyRNNtriton (StreamingLucyRNN "
+                            f"takes the native LucyRNN), got {type(model).__name__}")
+        cfg = model.config
+        if model.num_tracks > 1:
+            raise ValueError(f"streaming: num_tracks = {model.num_tracks} > 1 is not supported" + alt)
+        if cfg.hidden_dim % 16 != 0:
+            raise ValueError(f"streaming: hidden_dim {cfg.hidden_dim} is not a multiple of 16" + alt)
+        if cfg.hidden_dim > 2048 or cfg.input_dim > 2048:
+            raise ValueError(f"streaming: hidden_dim {cfg.hidden_dim} / input_dim {cfg.input_dim} "
+                             "above 2048 (a workgroup keeps its input rows in LDS)" + alt)
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("streaming: weights fp32 or bf16")
+        if schedule not in ("wavefront", "frame"):
+            raise ValueError("schedule must be 'wavefront' or 'frame'")
+        dev = next(model.parameters()).device
+        ops._lib.require_device(next(model.parameters()))
+        self.cfg, self.B, self.K, self.dtype, self.blank = cfg, batch, frames_per_call, dtype, blank
+        self.L, self.D, self.V, self.Din = cfg.num_layers, cfg.hidden_dim, cfg.vocab_size, cfg.input_dim
+        self.schedule = schedule
+        L, D, B, K = self.L, self.D, batch, frames_per_call
+        f32 = torch.float32
+        fb = lambda t: t.detach().float().contiguous()   # noqa: E731
+        # layer 0's weight columns and the x buffer zero-padded to 8: exact, the zeros add nothing
+        self.Dp = (self.Din + 7) // 8 * 8
+        norms = model.norms[0]
+        self.eps = float(norms[0].eps) if len(norms) else 1e-5
+        if any(float(n.eps) != self.eps for n in norms):
+            raise ValueError("streaming: the inter-layer LayerNorms must share one eps" + alt)
+        self.layers = []
+        for l, cell in enumerate(model.tracks[0]):
+            wl = cell.linear.weight.detach()
+            if l == 0 and self.Dp != self.Din:
+                wl = torch.nn.functional.pad(wl, (0, self.Dp - self.Din))
+            bl = cell.linear.bias
+            self.layers.append({
+                "w": wl.to(dtype).contiguous(),
+                "b": fb(bl) if bl is not None else torch.zeros(7 * D, dtype=f32, device=dev),
+                "ln": (fb(norms[l - 1].weight), fb(norms[l - 1].bias)) if l > 0 else None})
+        self.w_out = model.output_proj.weight.detach().to(dtype).contiguous()
+        ob = model.output_proj.bias
+        self.b_out = fb(ob) if ob is not None else torch.zeros(self.V, dtype=f32, device=dev)
+        self.joiner = joiner is not None
         if self.joiner:
-            self._rnnt_block()
+            self._init_joiner(joiner, max_symbols, dev)
+        z = lambda *s: torch.zeros(*s, dtype=f32, device=dev)   # noqa: E731
+        self.x = z(K, B, self.Dp)
+        self.mask = torch.ones(K, B, dtype=f32, device=dev)
+        self.h = [z(B, D) for _ in range(L)]
+        self.s = [z(B, D) for _ in range(L)]
+        # layer l < L - 1: output and records per frame parity; the last layer's output per frame
+        self.xo = [(z(B, D), z(B, D)) for _ in range(L - 1)]
+        self.rec = [(z(D // 16, B, 4), z(D // 16, B, 4)) for _ in range(L - 1)]
+        self.xlast = z(K, B, D)
+        self.logits = z(K, B, self.V)
+        self.emit = torch.full((K, B), -1, dtype=torch.int32, device=dev)
+        self.prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        if self.joiner:
+            self.enc_p = z(K, B, self.J)
+        self.graph = None
+        if graph:
+            self._capture()
+        self.reset()
 
-    def _capture(self):
-        side = torch.cuda.Stream(self.x.device)
-        side.wait_stream(torch.cuda.current_stream(self.x.device))
-        with torch.cuda.stream(side):   # warm-up: library workspaces, kernel loading
-            self._block()
-        torch.cuda.current_stream(self.x.device).wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph):
-            self._block()
+    def _layer_args(self, l, j):
+        """The arguments of layer l at frame j of the block (ops.lucy_tframe_layer / tframe_job)."""
+        e, p, last = self.layers[l], j & 1, l == self.L - 1
+        kw = dict(mask=self.mask[j], st_out=None if last else self.rec[l][p])
+        if l > 0:
+            kw.update(ln=e["ln"], st_in=self.rec[l - 1][p])
+        return (self.x[j] if l == 0 else self.xo[l - 1][p], e["w"], e["b"], self.h[l], self.s[l],
+                self.xlast[j] if last else self.xo[l][p]), kw
 
-    # ------------------------------------------------------------------------------- API ---
-    def reset(self, hidden_states=None, streams=None):
-        """Start streams afresh: state from ``hidden_states`` ((h list, s list) of [B,D], as the
-        reference's forward takes) or zero, prev token = none (``blank`` with a joiner).
-        ``streams``: index tensor/list of the streams to reset (default all)."""
-        idx = slice(None) if streams is None else torch.as_tensor(streams, device=self.x.device)
+    def _frame(self, j):
         for l in range(self.L):
-            for buf, src in ((self.h[l], None if hidden_states is None else hidden_states[0][l]),
-                             (self.s[l], None if hidden_states is None else hidden_states[1][l])):
-                if src is None:
-                    buf[idx] = 0.0
-                else:
-                    buf[idx] = src.to(buf.device, torch.float32)[idx]
-        self.prev[idx] = self.blank if self.joiner else -1
+            args, kw = self._layer_args(l, j)
+            ops.lucy_tframe_layer(*args, eps=self.eps, **kw)
+        ops.lucy_frame_gemm(ops.FRAME_PLAIN, self.xlast[j], self.w_out, self.b_out, self.logits[j])
+        if not self.joiner:
+            ops.ctc_greedy_step(self.logits[j], self.prev, self.emit[j], mask=self.mask[j],
+                                blank=self.blank)
+
+    def _block_wavefront(self):
+        K, L, D = self.K, self.L, self.D
+        stream = ops._lib.stream_of(self.x)
+        for tau in range(K + L - 1):
+            jobs = []
+            for l in range(L):
+                if 0 <= tau - l < K:
+                    args, kw = self._layer_args(l, tau - l)
+                    jobs.append(ops.tframe_job(*args, **kw))
+            ops.lucy_tframe_layer_multi(self.w_out.dtype, jobs, stream, eps=self.eps)
+        ops.lucy_frame_gemm(ops.FRAME_PLAIN, self.xlast.view(K * self.B, D), self.w_out, self.b_out,
+                            self.logits.view(K * self.B, self.V))
+        if self.joiner:
+            return self._rnnt_block()
+        ops.ctc_greedy_frames(self.logits, self.prev, self.emit, mask=self.mask, blank=self.blank)
+
+    def _x_in(self):
+        return self.x[..., :self.Din]
+
+    def reset(self, hidden_states=None, streams=None):
+        """As StreamingLucyRNN.reset, with ``hidden_states`` in LucyRNNtriton's nesting
+        ([[h] * L], [[s] * L]) (what its forward returns and takes)."""
+        if hidden_states is not None:
+            hidden_states = (hidden_states[0][0], hidden_states[1][0])
+        super().reset(hidden_states, streams)
 
     def state(self):
-        """(h list, s list) fp32 copies — the reference's (h, s) return (lucyrnn.py:188-189)."""
-        return [t.clone() for t in self.h], [t.clone() for t in self.s]
-
-    def step(self, x, mask=None):
-        """Advance every stream by K = frames_per_call model frames.  x [B, K, input_dim *
-        stack_order] (already stacked); mask [B, K] (bool/float, None = all live).  Returns
-        emit int32 [B, K] on the device: the token decoder.py appends at that frame, or -1.
-        The logits of the block stay in ``self.logits`` ([K, B, V]).
-        With a joiner: returns (tokens int32 [B, K * max_symbols], frames, counts int32 [B]) on
-        the device instead: row b's first counts[b] tokens are this block's emissions, frames
-        their frame index within the block; later entries are stale."""
-        self.x.copy_(x.transpose(0, 1))
-        if mask is None:
-            self.mask.fill_(1.0)
-        else:
-            self.mask.copy_(mask.transpose(0, 1))
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self._block()
-        if self.joiner:
-            return self.tokens, self.tok_frames, self.counts
-        return self.emit.t()
-
-    def decode(self, feats, masks=None, return_logits=False):
-        """Whole utterances through the streaming path: feats [B, T, input_dim] raw frames,
-        stacked as the model does (lucyrnn.py:92-99: the tail T % stack_order is dropped, a
-        stacked frame is live when all its frames are).  Returns the decoder.py token lists
-        (and logits [B, T', V] if asked).  One host sync at the end."""
-        B, T, F = feats.shape
-        k = self.cfg.stack_order
-        Tt = T - T % k
-        x = feats[:, :Tt].reshape(B, Tt // k, F * k)
-        m = None
-        if masks is not None:
-            m = masks.reshape(B, -1)[:, :Tt].reshape(B, Tt // k, k).all(-1).float()
-        T2 = x.shape[1]
-        emits, logits = [], []
-        for t0 in range(0, T2, self.K):
-            n = min(self.K, T2 - t0)
-            xb = torch.zeros(B, self.K, x.shape[2], dtype=self.dtype, device=self.x.device)
-            xb[:, :n] = x[:, t0:t0 + n]
-            mb = torch.zeros(B, self.K, device=self.x.device)   # padding frames are masked out
-            mb[:, :n] = 1.0 if m is None else m[:, t0:t0 + n]
-            if self.joiner:
-                tk, _, ct = self.step(xb, mb)
-                emits.append(torch.cat([ct.unsqueeze(1), tk], 1))   # (a copy: count, tokens)
-            else:
-                emits.append(self.step(xb, mb)[:, :n].clone())
-            if return_logits:
-                logits.append(self.logits[:n].transpose(0, 1).clone())
-        em = torch.cat(emits, 1).cpu() if emits else torch.zeros(B, 0, dtype=torch.int32)
-        if self.joiner:
-            w = 1 + self.K * self.max_symbols
-            toks = [[t for k in range(0, em.shape[1], w) for t in row[k + 1:k + 1 + row[k]]]
-                    for row in em.tolist()]
-        else:
-            toks = [[int(t) for t in row if t >= 0] for row in em]
-        if return_logits:
-            return toks, torch.cat(logits, 1) if logits else None
-        return toks
+        """([[h] * L], [[s] * L]) fp32 copies: LucyRNNtriton.forward's ``hidden_states``."""
+        h, s = super().state()
+        return [h], [s]

@@ -8,7 +8,12 @@ Native LucyRNN 6 x 512, 80-d input, V = 1024 (the C2 shape, infer mode), B concu
     layer) + torch.argmax, i.e. what the reference does per frame on a GPU.
 Prints one JSON object per configuration: stream frames/s (B x frames / s) and ms per frame.
 
-usage: python tools/stream_bench.py [--frames 256] [--batches 1,16,64,256]
+--model triton: the same sweep for statecatcher_amd.StreamingLucyRNNtriton on a LucyRNNtriton of
+the same size (the model the training step runs), each line with the baseline a user had before
+it: LucyRNNtriton.forward on K-frame chunks with carried state + ctc_greedy_decode under
+torch.no_grad() (bf16: under autocast), measured in the same process (baseline_ms_per_frame).
+
+usage: python tools/stream_bench.py [--model native|triton] [--frames 256] [--batches 1,16,64,256]
 """
 import argparse
 import json
@@ -32,8 +37,68 @@ def timed(fn, n, warm=3):
     return time.perf_counter() - t0
 
 
+def chunked_offline(m, x, K, dt):
+    """Seconds per pass over x [B, N, F] as LucyRNNtriton.forward on K-frame chunks with carried
+    state, each followed by the offline greedy decode: what streaming a LucyRNNtriton took
+    before StreamingLucyRNNtriton."""
+    import statecatcher_amd as sc
+    B, N, _ = x.shape
+    lens = torch.full((B,), K, dtype=torch.int64, device=x.device)
+    chunks = [x[:, i:i + K].contiguous() for i in range(0, N, K)]
+    state = [None]
+    it = iter(range(10 ** 9))
+
+    @torch.no_grad()
+    def run():
+        c = chunks[next(it) % len(chunks)]
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=dt == torch.bfloat16):
+            lg, state[0] = m(c, state[0])
+        sc.ctc_greedy_decode(lg.float(), lens)
+    return timed(run, len(chunks))
+
+
+def main_triton(args):
+    import statecatcher_amd as sc
+    from statecatcher_amd.streaming import StreamingLucyRNNtriton
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    cfg = sc.LucyRNNConfig(input_dim=80, hidden_dim=512, num_layers=6, vocab_size=1024,
+                           kernel_impl="triton", fused_ops=True, layer_norm=False)
+    m = sc.LucyRNNtriton(cfg).to(dev)
+    with torch.no_grad():
+        m.output_proj.weight.normal_(0.0, 0.02)
+    N = args.frames
+    for B in [int(b) for b in args.batches.split(",")]:
+        x = torch.randn(B, N, 80, device=dev)
+        kgs = [(int(k), True) for k in args.ks.split(",")] + [(1, False)]
+        base = {}
+        for sched, dt, K, graph in [(s_, getattr(torch, d)) + kg for s_ in args.schedules.split(",")
+                                    for d in args.dtypes.split(",") for kg in kgs]:
+            if sched == "wavefront" and K == 1:
+                continue   # (one frame per block: the same launches as "frame")
+            if (dt, K) not in base:
+                base[(dt, K)] = chunked_offline(m, x, K, dt)
+            st = StreamingLucyRNNtriton(m, B, K, dtype=dt, graph=graph, schedule=sched)
+            blocks = [x[:, i:i + K].contiguous() for i in range(0, N, K)]
+            it = iter(range(10 ** 9))
+
+            def run():
+                st.step(blocks[next(it) % len(blocks)])
+            nb = N // K
+            dt_s = timed(run, nb)
+            print(json.dumps({"impl": f"hip_tframe_{sched}" + ("_graph" if graph else "_eager"),
+                              "dtype": str(dt).split(".")[-1], "B": B, "K": K, "frames": nb * K,
+                              "stream_frames_per_s": round(B * nb * K / dt_s, 1),
+                              "ms_per_frame": round(1e3 * dt_s / (nb * K), 4),
+                              "baseline_ms_per_frame": round(1e3 * base[(dt, K)] / (nb * K), 4)}),
+                  flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="native", choices=["native", "triton"],
+                    help="native: LucyRNN / StreamingLucyRNN; triton: LucyRNNtriton / "
+                         "StreamingLucyRNNtriton with the chunked offline baseline")
     ap.add_argument("--frames", type=int, default=256)
     ap.add_argument("--batches", default="1,16,64,256")
     ap.add_argument("--fused", type=int, default=0)
@@ -44,6 +109,8 @@ def main():
                     help="frame engine block schedules (StreamingLucyRNN schedule=)")
     ap.add_argument("--ks", default="1,8", help="frames per graph call")
     args = ap.parse_args()
+    if args.model == "triton":
+        return main_triton(args)
     import statecatcher_amd as sc
     from statecatcher_amd.streaming import StreamingLucyRNN
     dev = torch.device("cuda:0")
