@@ -884,6 +884,74 @@ int sc_rnnt_greedy_decode(const void* enc_p, const void* pred_tab, const void* W
                           int32_t* prev, int32_t* tokens, int32_t* frames, int cap,
                           int32_t* counts, void* stream);
 
+/*
+ * CTC prefix beam search, offline and chunked (csrc/ctc_beam.hip).  The reference's decoder.py is
+ * CTC greedy only (its README lists the beam search decoder as planned).  Greedy takes the best
+ * frame-wise path; prefix beam search sums every alignment of a hypothesis and returns an n-best
+ * list with scores.  All arithmetic is fp32; x (fp32 / bf16 / f16) is widened on load.
+ *   lae(a, b) = max(a, b) + log1p(exp(-|a - b|)),  lae(-inf, b) = b
+ * Per stream the state is an ordered beam of at most `beam` hypotheses: a token prefix, pb (log-
+ * probability of the prefix's alignments that end in blank) and pnb (those that end in a
+ * non-blank).  A reset stream holds the empty prefix with pb = 0, pnb = -inf.  For each live
+ * frame t in order (live as in sc_rnnt_greedy_decode: t < lengths[b] where lengths is given, and
+ * mask[b*mask_b + t*mask_t] != 0 where mask is given):
+ *   1. lp[v] = x[v] - logsumexp_v x (is_logits = 1) or x[v] (is_logits = 0)
+ *   2. the frame's tokens: the top_k non-blank v with the largest lp, ties to the lower index
+ *   3. stay candidates, one per beam entry in beam order:  tot = lae(pb, pnb);
+ *      pb' = tot + lp[blank];  pnb' = pnb + lp[last] if the prefix is non-empty and its last token
+ *      is one of the frame's tokens, else -inf
+ *   4. extension candidates, ordered by (beam rank, top_k rank), prefix l and token c:
+ *      pnb' = (c == last(l) ? pb : tot) + lp[c], pb' = -inf.  If l + c is already a beam entry the
+ *      extension is no candidate of its own: that entry's stay candidate gets
+ *      pnb' = lae(its repeat term, the extension's pnb').  Identity is decided by (64-bit rolling
+ *      hash of the tokens, length), not by comparing the token sequences.
+ *   5. candidates whose total lae(pb', pnb') is -inf are dropped; the `beam` largest totals (ties
+ *      to the earlier candidate in the order above), sorted by total descending, are the new beam.
+ * A NaN anywhere in a row makes that stream's result unspecified; the call still completes with
+ * every index in range (a NaN ranks last among the lp and a NaN total is dropped).
+ * Limits: 1 <= beam <= 32, 1 <= top_k <= min(32, V - 1), 1 <= nbest <= beam, V >= 2,
+ * 0 <= blank < V.
+ *
+ * The state is opaque device memory of sc_ctc_beam_state_bytes(B, beam, max_frames) bytes, 8-byte
+ * aligned, per stream: the beam (pb, pnb, trie node, hash, length, last token), the number of live
+ * frames consumed, a status word, and the token history as a parent-pointer trie of
+ * 1 + max_frames * beam (parent, token) nodes -- node 0 is the empty prefix, the extension kept at
+ * rank r of live frame f is node 1 + f * beam + r, so nothing is allocated or counted atomically.
+ *   sc_ctc_beam_reset   every stream (streams null) or those with streams[b] != 0 back to the
+ *                       fresh state.  Must run once before the first sc_ctc_beam_frames.
+ *   sc_ctc_beam_frames  consumes x [B][T][V] (element strides stride_b, stride_t, inner 1): a
+ *                       frame-parallel pre-pass (one wave per live row, the row read once: lp[blank]
+ *                       and the top_k (index, lp) pairs go to `workspace`, at least
+ *                       sc_ctc_beam_workspace_bytes(B, T, top_k) bytes, 4-byte aligned), then one
+ *                       workgroup per stream walks the frames.  May be called any number of times
+ *                       on one state with the same beam: a stream fed in chunks ends in the state
+ *                       of the stream fed whole.  The frame counter lives in the state and no
+ *                       argument changes from chunk to chunk, so a captured graph of one chunk call
+ *                       can be replayed.  Once a stream has consumed max_frames live frames, further
+ *                       live frames are ignored and status bit 0 is set.
+ *   sc_ctc_beam_result  reads the state (does not change it): for n < nbest, tokens[b][n][0..cap)
+ *                       int32 <- the first min(lens, cap) tokens of beam entry n, lens[b][n] <- its
+ *                       full token count (even beyond cap), scores[b][n] <- lae(pb, pnb).  Nothing is
+ *                       written at or beyond cap; entries past lens are left untouched.  For n at or
+ *                       past the number of hypotheses alive, lens = -1 and scores = -inf.
+ *                       status int32 [B] or null <- the status word (bit 0: max_frames reached;
+ *                       bit 1: the state was not made for this beam).
+ * B == 0 (and T == 0 for sc_ctc_beam_frames) launch nothing and return 0.  The size functions
+ * return 0 for arguments outside the limits.  No host sync, no allocation.
+ */
+size_t sc_ctc_beam_state_bytes(int B, int beam, int max_frames);
+size_t sc_ctc_beam_workspace_bytes(int B, int T, int top_k);
+int sc_ctc_beam_reset(void* state, size_t state_bytes, int B, int beam, int max_frames,
+                      const float* streams, void* stream);
+int sc_ctc_beam_frames(const void* x, int dtype, int is_logits, int B, int T, int V,
+                       int64_t stride_b, int64_t stride_t, const int64_t* lengths,
+                       const float* mask, int64_t mask_b, int64_t mask_t, int blank, int beam,
+                       int top_k, void* state, size_t state_bytes, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int sc_ctc_beam_result(const void* state, size_t state_bytes, int B, int beam, int nbest,
+                       int32_t* tokens, int cap, int32_t* lens, float* scores, int32_t* status,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@
 //   gemm_wgrad      LinearSafe / output_proj weight gradient           lucyrnn_triton.py:20-25, :107-109
 //   clip_adam_      clip_grad_norm_(params, max_norm) + optim.Adam/AdamW.step()  train.py:543-552
 //   rnnt_greedy_decode  (absent in the reference) greedy decode of RNNTPredictorJoiner  model.py:112-145
+//   ctc_beam_*      (absent in the reference: decoder.py is greedy only) CTC prefix beam search
 // There is no CPU kernel: calling an op on CPU tensors raises (no silent fallback).
 
 #include <ATen/ATen.h>
@@ -462,6 +463,138 @@ std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_meta(
   return {at::empty({B, cap}, io), at::empty({B}, io), at::empty({B, return_frames ? cap : 0}, io)};
 }
 
+// CTC prefix beam search (include/statecatcher.h, sc_ctc_beam_*).  The state is a uint8
+// [B, bytes per stream] tensor of ctc_beam_state_bytes(1, beam, max_frames) bytes per stream.
+void check_beam_state(const Tensor& state, const char* me) {
+  TORCH_CHECK(state.scalar_type() == at::kByte && state.dim() == 2 && state.is_contiguous(), me,
+              "state must be a contiguous uint8 [B, bytes per stream] tensor");
+}
+
+int64_t ctc_beam_state_bytes(int64_t B, int64_t beam, int64_t max_frames) {
+  TORCH_CHECK(B >= 0 && B <= INT32_MAX && max_frames >= 0 && max_frames <= INT32_MAX,
+              "statecatcher::ctc_beam_state_bytes: B or max_frames out of range");
+  const size_t n = sc_ctc_beam_state_bytes((int)B, (int)beam, (int)max_frames);
+  TORCH_CHECK(n != 0 || B == 0, "statecatcher::ctc_beam_state_bytes: beam=", beam, " (1..32), "
+              "max_frames=", max_frames, " do not describe a state");
+  return (int64_t)n;
+}
+
+void ctc_beam_reset_hip(Tensor& state, int64_t beam, int64_t max_frames,
+                        const optional<Tensor>& streams) {
+  c10::DeviceGuard guard(state.device());
+  const char* me = "statecatcher::ctc_beam_reset_: ";
+  check_beam_state(state, me);
+  const int64_t B = state.size(0);
+  if (streams && streams->defined())
+    TORCH_CHECK(streams->scalar_type() == at::kFloat && streams->numel() == B &&
+                streams->is_contiguous(), me, "streams must be contiguous fp32 [B]");
+  sc_check(sc_ctc_beam_reset(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
+                             (int)max_frames, (const float*)opt_ptr(streams), stream_for(state)),
+           "statecatcher::ctc_beam_reset_");
+}
+
+void ctc_beam_reset_meta(Tensor& state, int64_t beam, int64_t max_frames,
+                         const optional<Tensor>& streams) {}
+
+void ctc_beam_frames_hip(const Tensor& x_in, Tensor& state, const optional<Tensor>& lengths_in,
+                         const optional<Tensor>& mask, int64_t blank, int64_t beam, int64_t top_k,
+                         bool is_logits) {
+  c10::DeviceGuard guard(x_in.device());
+  const char* me = "statecatcher::ctc_beam_frames_: ";
+  TORCH_CHECK(x_in.dim() == 3, me, "x must be [B,T,V]");
+  check_beam_state(state, me);
+  Tensor x = x_in.stride(2) == 1 || x_in.numel() == 0 ? x_in : x_in.contiguous();
+  const int64_t B = x.size(0), T = x.size(1), V = x.size(2);
+  TORCH_CHECK(state.size(0) == B, me, "the state holds ", state.size(0), " streams, x has ", B);
+  optional<Tensor> lens;
+  if (lengths_in && lengths_in->defined()) {
+    lens = lengths_in->to(at::kLong).contiguous();
+    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
+  }
+  int64_t mb = 0, mt = 0;
+  if (mask && mask->defined()) {
+    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
+                mask->size(1) == T, me, "mask must be fp32 [B,T]");
+    mb = mask->stride(0);
+    mt = mask->stride(1);
+  }
+  TORCH_CHECK(B <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, me, "shape out of range");
+  const size_t ws_bytes = sc_ctc_beam_workspace_bytes((int)B, (int)T, (int)top_k);
+  Tensor ws = at::empty({(int64_t)ws_bytes}, x.options().dtype(at::kByte));
+  sc_check(sc_ctc_beam_frames(x.data_ptr(), dtype_code(x), is_logits ? 1 : 0, (int)B, (int)T, (int)V,
+                              x.stride(0), x.stride(1), (const int64_t*)opt_ptr(lens),
+                              (const float*)opt_ptr(mask), mb, mt, (int)blank, (int)beam, (int)top_k,
+                              state.data_ptr(), (size_t)state.numel(), ws.data_ptr(), ws_bytes,
+                              stream_for(x)),
+           "statecatcher::ctc_beam_frames_");
+}
+
+void ctc_beam_frames_meta(const Tensor& x, Tensor& state, const optional<Tensor>& lengths,
+                          const optional<Tensor>& mask, int64_t blank, int64_t beam, int64_t top_k,
+                          bool is_logits) {
+  TORCH_CHECK(x.dim() == 3 && state.dim() == 2 && state.size(0) == x.size(0),
+              "statecatcher::ctc_beam_frames_: x [B,T,V], state [B, bytes per stream]");
+}
+
+// tokens [B,nbest,cap] (-1 where nothing is written), lens [B,nbest], scores [B,nbest], status [B]
+std::tuple<Tensor, Tensor, Tensor, Tensor> ctc_beam_result_hip(const Tensor& state, int64_t beam,
+                                                               int64_t nbest, int64_t cap) {
+  c10::DeviceGuard guard(state.device());
+  const char* me = "statecatcher::ctc_beam_result: ";
+  check_beam_state(state, me);
+  TORCH_CHECK(nbest >= 0 && nbest <= INT32_MAX && cap >= 0 && cap <= INT32_MAX, me,
+              "nbest or cap out of range");
+  const int64_t B = state.size(0);
+  auto io = state.options().dtype(at::kInt);
+  Tensor tokens = at::full({B, nbest, cap}, -1, io), lens = at::empty({B, nbest}, io);
+  Tensor scores = at::empty({B, nbest}, state.options().dtype(at::kFloat));
+  Tensor status = at::empty({B}, io);
+  sc_check(sc_ctc_beam_result(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam, (int)nbest,
+                              (int32_t*)tokens.data_ptr(), (int)cap, (int32_t*)lens.data_ptr(),
+                              (float*)scores.data_ptr(), (int32_t*)status.data_ptr(),
+                              stream_for(state)),
+           "statecatcher::ctc_beam_result");
+  return {tokens, lens, scores, status};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> ctc_beam_result_meta(const Tensor& state, int64_t beam,
+                                                                int64_t nbest, int64_t cap) {
+  TORCH_CHECK(state.dim() == 2 && nbest >= 0 && cap >= 0,
+              "statecatcher::ctc_beam_result: state [B, bytes per stream], nbest, cap >= 0");
+  const int64_t B = state.size(0);
+  auto io = state.options().dtype(at::kInt);
+  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
+          at::empty({B, nbest}, state.options().dtype(at::kFloat)), at::empty({B}, io)};
+}
+
+// offline: a fresh state for max_frames (default T) live frames, the frames, the result
+std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_hip(
+    const Tensor& x, const optional<Tensor>& lengths, const optional<Tensor>& mask, int64_t blank,
+    int64_t beam, int64_t top_k, int64_t nbest, bool is_logits, optional<int64_t> max_frames_in,
+    optional<int64_t> cap_in) {
+  c10::DeviceGuard guard(x.device());
+  TORCH_CHECK(x.dim() == 3, "statecatcher::ctc_beam_decode: x must be [B,T,V]");
+  const int64_t B = x.size(0), max_frames = max_frames_in ? *max_frames_in : x.size(1);
+  const int64_t per = ctc_beam_state_bytes(1, beam, max_frames);
+  Tensor state = at::empty({B, per}, x.options().dtype(at::kByte));
+  ctc_beam_reset_hip(state, beam, max_frames, c10::nullopt);
+  ctc_beam_frames_hip(x, state, lengths, mask, blank, beam, top_k, is_logits);
+  auto r = ctc_beam_result_hip(state, beam, nbest, cap_in ? *cap_in : max_frames);
+  return {std::get<0>(r), std::get<1>(r), std::get<2>(r)};
+}
+
+std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_meta(
+    const Tensor& x, const optional<Tensor>& lengths, const optional<Tensor>& mask, int64_t blank,
+    int64_t beam, int64_t top_k, int64_t nbest, bool is_logits, optional<int64_t> max_frames_in,
+    optional<int64_t> cap_in) {
+  TORCH_CHECK(x.dim() == 3 && nbest >= 0, "statecatcher::ctc_beam_decode: x must be [B,T,V]");
+  const int64_t B = x.size(0), max_frames = max_frames_in ? *max_frames_in : x.size(1);
+  const int64_t cap = cap_in ? *cap_in : max_frames;
+  auto io = x.options().dtype(at::kInt);
+  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
+          at::empty({B, nbest}, x.options().dtype(at::kFloat))};
+}
+
 // ------------------------------------------------------------------------------ mLSTM --------
 // q, k [B,NH,T,DQ], v [B,NH,T,DV] (bf16 / f16, contiguous), igate / fgate fp32 [B,NH,T]: the
 // chunkwise cell of the xLSTM encoder (model.py:214-229; the fork's mlstm_kernels).
@@ -867,6 +1000,15 @@ TORCH_LIBRARY(statecatcher, m) {
         "Tensor? lengths=None, Tensor? mask=None, int blank=0, int max_symbols=4, "
         "Tensor(a!)? prev=None, int? cap=None, bool return_frames=False)"
         " -> (Tensor tokens, Tensor counts, Tensor frames)");
+  m.def("ctc_beam_state_bytes(int B, int beam, int max_frames) -> int", &ctc_beam_state_bytes);
+  m.def("ctc_beam_reset_(Tensor(a!) state, int beam, int max_frames, Tensor? streams=None) -> ()");
+  m.def("ctc_beam_frames_(Tensor x, Tensor(a!) state, Tensor? lengths=None, Tensor? mask=None, "
+        "int blank=0, int beam=8, int top_k=8, bool is_logits=False) -> ()");
+  m.def("ctc_beam_result(Tensor state, int beam, int nbest=1, int cap=0)"
+        " -> (Tensor tokens, Tensor lens, Tensor scores, Tensor status)");
+  m.def("ctc_beam_decode(Tensor x, Tensor? lengths=None, Tensor? mask=None, int blank=0, "
+        "int beam=8, int top_k=8, int nbest=1, bool is_logits=False, int? max_frames=None, "
+        "int? cap=None) -> (Tensor tokens, Tensor lens, Tensor scores)");
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
@@ -889,6 +1031,10 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("gemm_wgrad", &gemm_wgrad_hip);
   m.impl("clip_adam_", &clip_adam_hip);
   m.impl("rnnt_greedy_decode", &rnnt_greedy_decode_hip);
+  m.impl("ctc_beam_reset_", &ctc_beam_reset_hip);
+  m.impl("ctc_beam_frames_", &ctc_beam_frames_hip);
+  m.impl("ctc_beam_result", &ctc_beam_result_hip);
+  m.impl("ctc_beam_decode", &ctc_beam_decode_hip);
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
@@ -911,4 +1057,8 @@ TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("gemm_wgrad", &gemm_wgrad_meta);
   m.impl("clip_adam_", &clip_adam_meta);
   m.impl("rnnt_greedy_decode", &rnnt_greedy_decode_meta);
+  m.impl("ctc_beam_reset_", &ctc_beam_reset_meta);
+  m.impl("ctc_beam_frames_", &ctc_beam_frames_meta);
+  m.impl("ctc_beam_result", &ctc_beam_result_meta);
+  m.impl("ctc_beam_decode", &ctc_beam_decode_meta);
 }

@@ -2,7 +2,7 @@
 and the transducer counterpart the reference does not have."""
 import torch
 
-from .ops import ctc_greedy_decode, rnnt_greedy_decode
+from .ops import ctc_beam_decode, ctc_greedy_decode, rnnt_greedy_decode
 
 
 def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
@@ -11,6 +11,26 @@ def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
     tokens = tokens.cpu()
     counts = counts.cpu().tolist()
     return [tokens[b, :c].tolist() for b, c in enumerate(counts)]
+
+
+def ctc_beam_decoder(log_probs, input_lengths, blank=0, beam=8, top_k=8, nbest=1,
+                     return_scores=False):
+    """CTC prefix beam search of log_probs [B,T,V] (ops.ctc_beam_decode: every frame extends each
+    hypothesis by its top_k likeliest tokens and keeps the ``beam`` best).  nbest=1 returns the
+    List[List[int]] of ctc_greedy_decoder; nbest>1 a list per stream of up to nbest token lists,
+    best first.  return_scores adds the log-probabilities in the same nesting.  One host copy at
+    the end."""
+    tokens, lens, scores = ctc_beam_decode(log_probs, input_lengths, blank=blank, beam=beam,
+                                           top_k=top_k, nbest=nbest)
+    B, N, cap = tokens.shape
+    packed = torch.cat([lens.unsqueeze(2), scores.view(torch.int32).unsqueeze(2), tokens], 2).cpu()
+    lens, scores = packed[:, :, 0].tolist(), packed[:, :, 1].contiguous().view(torch.float32).tolist()
+    hyps = [[packed[b, n, 2:2 + lens[b][n]].tolist() for n in range(N) if lens[b][n] >= 0]
+            for b in range(B)]
+    scs = [[scores[b][n] for n in range(N) if lens[b][n] >= 0] for b in range(B)]
+    if nbest == 1:
+        hyps, scs = [h[0] if h else [] for h in hyps], [s[0] if s else float("-inf") for s in scs]
+    return (hyps, scs) if return_scores else hyps
 
 
 def rnnt_joiner_tables(joiner, dtype=None):

@@ -1370,6 +1370,143 @@ def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=
     return (tokens, counts, frames) if return_frames else (tokens, counts)
 
 
+class CtcBeamState:
+    """The state of B CTC prefix beam search streams (include/statecatcher.h, sc_ctc_beam_*):
+    ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its
+    status word and its token trie for ``max_frames`` live frames.  Made reset; ``reset()`` starts
+    every stream afresh, ``reset(streams)`` the listed stream indices (or, given a fp32 [B]
+    tensor, the streams whose entry is non-zero; no allocation then)."""
+
+    def __init__(self, B, beam, max_frames, device):
+        lib = _lib.load()
+        B, beam, max_frames = int(B), int(beam), int(max_frames)
+        nbytes = lib.sc_ctc_beam_state_bytes(max(B, 1), beam, max_frames)
+        if B < 0 or nbytes == 0:
+            raise ValueError(f"ctc_beam_state: B={B}, beam={beam} (1..32), max_frames={max_frames} "
+                             "(>= 0, max_frames * beam < 2^31) do not describe a state")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("statecatcher ops run only on a ROCm GPU (HIP); got device "
+                               f"{device}. There is no CPU fallback.")
+        self.B, self.beam, self.max_frames = B, beam, max_frames
+        self.buf = torch.zeros(B, nbytes // max(B, 1), dtype=torch.uint8, device=device)
+        self._ws = None
+        self.reset()
+
+    @property
+    def nbytes(self):
+        return self.buf.numel()
+
+    def reset(self, streams=None):
+        if streams is not None and not isinstance(streams, torch.Tensor):
+            m = torch.zeros(self.B, dtype=torch.float32)
+            m[list(streams)] = 1.0
+            streams = m.to(self.buf.device, non_blocking=True)
+        if streams is not None and (streams.dtype != torch.float32 or streams.numel() != self.B
+                                    or not streams.is_contiguous()):
+            raise ValueError("ctc_beam_state.reset: streams must be contiguous fp32 [B]")
+        require_device(streams)
+        rc = _lib.load().sc_ctc_beam_reset(ptr(self.buf), self.nbytes, self.B, self.beam,
+                                           self.max_frames, ptr(streams), stream_of(self.buf))
+        check(rc, "sc_ctc_beam_reset")
+
+    def workspace(self, nbytes):
+        """The pre-pass workspace, grown when a call needs more (kept between calls, so a chunk
+        call of a fixed shape allocates once)."""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.buf.device)
+        return self._ws
+
+
+def ctc_beam_state(B, beam, max_frames, device):
+    """A reset CtcBeamState for chunked ctc_beam_decode: B streams, beam width ``beam``, room for
+    ``max_frames`` live frames per stream."""
+    return CtcBeamState(B, beam, max_frames, device)
+
+
+def ctc_beam_result(state, nbest=1, cap=None, out=None, return_status=False):
+    """The first ``nbest`` hypotheses of every stream of ``state`` (sc_ctc_beam_result; the state
+    is not changed) -> (tokens int32 [B,nbest,cap], lens int32 [B,nbest], scores fp32 [B,nbest]
+    [, status int32 [B]]).  The first min(lens, cap) entries of tokens[b,n] are valid and the
+    rest is -1; lens is the full token count; a rank with no hypothesis has lens -1 and score
+    -inf.  cap defaults to state.max_frames, which cannot overflow.  out = (tokens, lens, scores):
+    write into these instead of allocating (tokens is not filled then).  status bit 0: the stream
+    met more than max_frames live frames and ignored the rest."""
+    B, nbest = state.B, int(nbest)
+    dev = state.buf.device
+    if out is not None:
+        tokens, lens, scores = out
+        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 3 \
+            and tuple(tokens.shape[:2]) == (B, nbest) and lens.dtype == torch.int32 \
+            and lens.is_contiguous() and tuple(lens.shape) == (B, nbest) \
+            and scores.dtype == torch.float32 and scores.is_contiguous() \
+            and tuple(scores.shape) == (B, nbest)
+        if not ok:
+            raise ValueError("ctc_beam_result: out = (tokens int32 [B,nbest,cap], lens int32 "
+                             "[B,nbest], scores fp32 [B,nbest]), contiguous")
+        require_device(tokens, lens, scores)
+        cap = tokens.shape[2]
+    else:
+        cap = state.max_frames if cap is None else int(cap)
+        if cap < 0 or nbest < 0:
+            raise ValueError(f"ctc_beam_result: cap={cap} or nbest={nbest} is negative")
+        tokens = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    rc = _lib.load().sc_ctc_beam_result(ptr(state.buf), state.nbytes, B, state.beam, nbest,
+                                        ptr(tokens), cap, ptr(lens), ptr(scores), ptr(status),
+                                        stream_of(state.buf))
+    check(rc, "sc_ctc_beam_result")
+    return (tokens, lens, scores, status) if return_status else (tokens, lens, scores)
+
+
+def ctc_beam_decode(log_probs_or_logits, lengths=None, mask=None, blank=0, beam=8, top_k=8, nbest=1,
+                    is_logits=False, state=None, max_frames=None, cap=None, out=None):
+    """CTC prefix beam search (sc_ctc_beam_*, csrc/ctc_beam.hip; the contract is in
+    include/statecatcher.h) over x [B,T,V] (fp32 / bf16 / f16, unit inner stride): log-probs, or
+    logits with is_logits (the log-softmax is fused).  Each frame extends every hypothesis by the
+    ``top_k`` likeliest non-blank tokens and keeps the ``beam`` best; all arithmetic is fp32.
+    lengths int64 [B] (tensor or list) and mask fp32 [B,T] (0 = dead frame) are optional.
+
+    state=None decodes offline: a fresh state with room for max_frames (default T) live frames,
+    the frames, the result.  With a ``ctc_beam_state`` the call consumes x as the next chunk of
+    every stream (the state's own beam width is used) and returns the result so far; a stream
+    fed in chunks gives exactly the result of the stream fed whole.
+
+    Returns ctc_beam_result(state, nbest, cap, out): (tokens int32 [B,nbest,cap], lens int32
+    [B,nbest], scores fp32 [B,nbest]), hypotheses best first.  With a state and out= the call
+    allocates nothing once the state's workspace has its size (safe inside a hipGraph capture).
+    No host sync (a ``lengths`` list is copied to the device asynchronously)."""
+    x = log_probs_or_logits
+    require_device(x, mask)
+    if x.dim() != 3:
+        raise ValueError(f"ctc_beam_decode: x must be [B,T,V], got {tuple(x.shape)}")
+    B, T, V = x.shape
+    if x.numel() and x.stride(2) != 1:
+        x = x.contiguous()
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
+        raise ValueError("ctc_beam_decode: mask must be fp32 [B, T]")
+    lens = None if lengths is None else _as_len_tensor(lengths, x.device)
+    if lens is not None and lens.numel() != B:
+        raise ValueError("ctc_beam_decode: lengths must have B entries")
+    if state is None:
+        state = CtcBeamState(B, beam, T if max_frames is None else max_frames, x.device)
+    elif state.B != B or state.buf.device != x.device:
+        raise ValueError(f"ctc_beam_decode: the state holds {state.B} streams on "
+                         f"{state.buf.device}, x has {B} on {x.device}")
+    lib = _lib.load()
+    ws_bytes = lib.sc_ctc_beam_workspace_bytes(B, T, int(top_k))
+    ws = state.workspace(ws_bytes)
+    rc = lib.sc_ctc_beam_frames(
+        ptr(x), dtype_code(x), 1 if is_logits else 0, B, T, V, x.stride(0), x.stride(1),
+        ptr(lens), ptr(mask), mask.stride(0) if mask is not None else 0,
+        mask.stride(1) if mask is not None else 0, int(blank), state.beam, int(top_k),
+        ptr(state.buf), state.nbytes, ptr(ws), ws.numel(), stream_of(x))
+    check(rc, "sc_ctc_beam_frames")
+    return ctc_beam_result(state, nbest, cap, out)
+
+
 # ------------------------------------------------------------------- feature frontend --------
 def fbank(audio, kind="mfcc", sample_rate=16000):
     """make_frontend(kind)(audio).transpose(-1, -2) on the GPU (fbank.hip): audio fp32

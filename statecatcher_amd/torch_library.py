@@ -21,6 +21,7 @@ Reference interfaces (what a ``train.py`` user swaps in):
   gemm_wgrad  <- LinearSafe / output_proj weight gradient             lucyrnn_triton.py:20-25, :107-109
   clip_adam_  <- clip_grad_norm_(params, 50) + optim.Adam/AdamW.step() train.py:543-552
   rnnt_greedy_decode <- (absent in the reference) greedy decode of RNNTPredictorJoiner, model.py:112-145
+  ctc_beam_decode <- (absent in the reference: decoder.py is greedy only) CTC prefix beam search
 """
 import os
 
@@ -30,7 +31,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_torch_ops.
 OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay_scan_bwd",
        "layer_norm_fwd", "layer_norm_bwd", "ctc_fwd", "ctc_bwd", "ctc_mean", "ctc_greedy_decode",
        "mlstm_fwd", "mlstm_bwd", "mlstm_gate_bwd", "rnnt_joint_fwd", "rnnt_joint_bwd",
-       "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode")
+       "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode", "ctc_beam_state_bytes",
+       "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode")
 
 _LOADED = False
 
@@ -242,6 +244,40 @@ def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=
     tokens, counts, frames = load().rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths, mask,
                                                        blank, max_symbols, prev, cap, return_frames)
     return (tokens, counts, frames) if return_frames else (tokens, counts)
+
+
+def ctc_beam_decode(x, lengths=None, mask=None, blank=0, beam=8, top_k=8, nbest=1, is_logits=False,
+                    max_frames=None, cap=None):
+    """(tokens int32 [B,nbest,cap], lens int32 [B,nbest], scores fp32 [B,nbest]) of the offline
+    CTC prefix beam search (ops.ctc_beam_decode with state=None)."""
+    return load().ctc_beam_decode(x, lengths, mask, blank, beam, top_k, nbest, is_logits,
+                                  max_frames, cap)
+
+
+def ctc_beam_state(B, beam, max_frames, device):
+    """A reset state tensor (uint8 [B, bytes per stream]) for ctc_beam_frames_ / ctc_beam_result."""
+    sc = load()
+    state = torch.zeros(B, sc.ctc_beam_state_bytes(1, beam, max_frames), dtype=torch.uint8,
+                        device=device)
+    sc.ctc_beam_reset_(state, beam, max_frames)
+    return state
+
+
+def ctc_beam_reset_(state, beam, max_frames, streams=None):
+    """Every stream of ``state`` (or those with a non-zero entry in streams fp32 [B]) afresh."""
+    load().ctc_beam_reset_(state, beam, max_frames, streams)
+    return state
+
+
+def ctc_beam_frames_(x, state, lengths=None, mask=None, blank=0, beam=8, top_k=8, is_logits=False):
+    """Consume x [B,T,V] as the next chunk of every stream of ``state``, in place."""
+    load().ctc_beam_frames_(x, state, lengths, mask, blank, beam, top_k, is_logits)
+    return state
+
+
+def ctc_beam_result(state, beam, nbest=1, cap=0):
+    """(tokens [B,nbest,cap], lens [B,nbest], scores [B,nbest], status [B]) of a state."""
+    return load().ctc_beam_result(state, beam, nbest, cap)
 
 
 def gemm_tn(a, b, tile_m=0):
