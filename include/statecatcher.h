@@ -38,6 +38,8 @@
  *                        :144); the log_softmax of model.py:93 optionally fused
  *   sc_rnnt_greedy_decode <- (absent in the reference: decoder.py is CTC only) greedy decoding
  *                        of RNNTPredictorJoiner (model.py:112-145), offline and streaming
+ *   sc_rnnt_beam_*    <- (absent in the reference) transducer beam search of the same joiner,
+ *                        n-best with scores, offline and chunked
  */
 #ifndef STATECATCHER_H
 #define STATECATCHER_H
@@ -951,6 +953,82 @@ int sc_ctc_beam_frames(const void* x, int dtype, int is_logits, int B, int T, in
 int sc_ctc_beam_result(const void* state, size_t state_bytes, int B, int beam, int nbest,
                        int32_t* tokens, int cap, int32_t* lens, float* scores, int32_t* status,
                        void* stream);
+
+/*
+ * Transducer beam search for the stateless predictor, offline and chunked (csrc/rnnt_beam.hip).
+ * sc_rnnt_greedy_decode follows one path and returns no score; this is the time-synchronous beam
+ * search over the same joint, with an n-best list and scores.  Inputs are those of
+ * sc_rnnt_greedy_decode: enc_p [B][T][J] (strides stride_b, stride_t, inner 1), pred_tab [V][J]
+ * and W [V][J] contiguous, all of `dtype` (fp32 / bf16 / f16) and widened on load; bias fp32 [V];
+ * lengths, mask and blank with the same meaning.  All arithmetic is fp32:
+ *   z = tanh(enc_p[b][t] + pred_tab[u]) in the greedy kernel's form, u = the last token of the
+ *   prefix (`blank` for the empty prefix);  logit = W z + bias;  lp = logit - logsumexp_v logit;
+ *   lae as in the CTC beam search above.
+ * Parameters: 1 <= beam <= 32;  1 <= top_k <= 32, clipped to V - 1;  1 <= max_symbols <= 8, the
+ * most tokens one frame may emit;  1 <= nbest <= beam;  V >= 1;  1 <= J <= 256;  0 <= blank < V.
+ * Per stream the state is an ordered beam of at most `beam` entries (prefix, score); a reset stream
+ * holds [(empty, 0)].  For each live frame in order:
+ *   A = [] (ordered, capacity beam * (max_symbols + 1));  C = the beam
+ *   for r = 0 .. max_symbols:
+ *     for each (p, s) of C in order:  s' = s + lp_p[blank];  if p is already in A, that entry's
+ *       score becomes lae(entry, s'), else (p, s') is appended to A
+ *     if r == max_symbols: stop
+ *     D = for each (p, s) of C in order, for each of its top_k non-blank tokens c (lp descending,
+ *       ties to the lower index, NaN last), in that order: (p + c, s + lp_p[c]);  entries whose
+ *       score is -inf or NaN are dropped
+ *     C = the `beam` largest of D (ties to the earlier candidate), sorted descending;  empty: stop
+ *   A entries whose score is -inf or NaN are dropped;  the beam = the `beam` largest of A (ties to
+ *   the earlier insertion), sorted descending
+ * Within one D no two candidates spell the same prefix, so merging happens only into A; identity
+ * in A is (64-bit rolling hash of the tokens, length), with the CTC beam search's hash.  With
+ * nothing pruned the score of a prefix is exactly log P(prefix | x) over every alignment with at
+ * most max_symbols emissions per frame.  A NaN makes the affected stream's result unspecified
+ * (possibly empty, lens -1); orders stay total, every index stays in range, the call completes.
+ *
+ * The state is opaque device memory of sc_rnnt_beam_state_bytes(B, beam, max_symbols, max_frames)
+ * bytes, 8-byte aligned, per stream: the beam (score, trie node, hash, length, last token), the
+ * number of live frames consumed, a status word, and the token history as a parent-pointer trie of
+ * 1 + max_frames * max_symbols * beam (parent, token) nodes -- node 0 is the empty prefix, the
+ * candidate kept at rank k of round r of live frame f is node 1 + (f * max_symbols + r) * beam + k,
+ * so nothing is allocated or counted atomically and a token's frame is read off its node.
+ *   sc_rnnt_beam_reset   every stream (streams null) or those with streams[b] != 0 back to the
+ *                        fresh state.  Must run once before the first sc_rnnt_beam_frames.
+ *   sc_rnnt_beam_frames  one persistent workgroup per stream consumes the call's T frames.
+ *                        `workspace`: at least sc_rnnt_beam_workspace_bytes(B, V) bytes, 4-byte
+ *                        aligned (the logit image of the path that reads W from memory).  J == 64
+ *                        and V <= 1024 (W 16-byte aligned) keeps a row of W per lane in registers;
+ *                        any other V and J <= 256 reads W from memory.  beam and max_symbols must be
+ *                        the state's.  May be called any number of times on one state: a stream fed
+ *                        in chunks ends in the state of the stream fed whole.  The frame counter
+ *                        lives in the state and no argument changes from chunk to chunk, so a
+ *                        captured graph of one chunk call can be replayed.  Once a stream has
+ *                        consumed max_frames live frames, further live frames are ignored and
+ *                        status bit 0 is set.
+ *   sc_rnnt_beam_result  reads the state (does not change it): for n < nbest, tokens[b][n][0..cap)
+ *                        int32 <- the first min(lens, cap) tokens of beam entry n, frames (or null)
+ *                        likewise <- the ordinal, counted since reset, of the live frame at which
+ *                        each token was emitted (a merged hypothesis keeps the history of the entry
+ *                        first inserted into A), lens[b][n] <- the full token count (even beyond
+ *                        cap), scores[b][n] <- the score.  Nothing is written at or beyond cap;
+ *                        entries past lens are left untouched.  For n at or past the number of
+ *                        hypotheses alive, lens = -1 and scores = -inf.  status int32 [B] or null <-
+ *                        the status word (bit 0: max_frames reached; bit 1: the state was not made
+ *                        for this beam and max_symbols).
+ * B == 0 (and T == 0 for sc_rnnt_beam_frames) launch nothing and return 0.  The size functions
+ * return 0 for arguments outside the limits.  No host sync, no allocation.
+ */
+size_t sc_rnnt_beam_state_bytes(int B, int beam, int max_symbols, int max_frames);
+size_t sc_rnnt_beam_workspace_bytes(int B, int V);
+int sc_rnnt_beam_reset(void* state, size_t state_bytes, int B, int beam, int max_symbols,
+                       int max_frames, const float* streams, void* stream);
+int sc_rnnt_beam_frames(const void* enc_p, const void* pred_tab, const void* W, int dtype,
+                        const float* bias, int B, int T, int V, int J, int64_t stride_b,
+                        int64_t stride_t, const int64_t* lengths, const float* mask, int64_t mask_b,
+                        int64_t mask_t, int blank, int beam, int top_k, int max_symbols, void* state,
+                        size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream);
+int sc_rnnt_beam_result(const void* state, size_t state_bytes, int B, int beam, int max_symbols,
+                        int nbest, int32_t* tokens, int32_t* frames, int cap, int32_t* lens,
+                        float* scores, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -145,6 +145,14 @@ _SIGS = {
                                   _vp]),
     "sc_ctc_beam_result": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _vp, _i32, _vp, _fp, _vp,
                                   _vp]),
+    "sc_rnnt_beam_state_bytes": (_c.c_size_t, [_i32, _i32, _i32, _i32]),
+    "sc_rnnt_beam_workspace_bytes": (_c.c_size_t, [_i32, _i32]),
+    "sc_rnnt_beam_reset": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _i32, _fp, _vp]),
+    "sc_rnnt_beam_frames": (_i32, [_vp, _vp, _vp, _i32, _fp, _i32, _i32, _i32, _i32, _i64, _i64,
+                                   _vp, _fp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _c.c_size_t,
+                                   _vp, _c.c_size_t, _vp]),
+    "sc_rnnt_beam_result": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
+                                   _fp, _vp, _vp]),
 }
 EXPORTED = tuple(_SIGS)
 

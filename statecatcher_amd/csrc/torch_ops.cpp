@@ -21,6 +21,7 @@
 //   clip_adam_      clip_grad_norm_(params, max_norm) + optim.Adam/AdamW.step()  train.py:543-552
 //   rnnt_greedy_decode  (absent in the reference) greedy decode of RNNTPredictorJoiner  model.py:112-145
 //   ctc_beam_*      (absent in the reference: decoder.py is greedy only) CTC prefix beam search
+//   rnnt_beam_*     (absent in the reference) transducer beam search of RNNTPredictorJoiner
 // There is no CPU kernel: calling an op on CPU tensors raises (no silent fallback).
 
 #include <ATen/ATen.h>
@@ -595,6 +596,154 @@ std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_meta(
           at::empty({B, nbest}, x.options().dtype(at::kFloat))};
 }
 
+// Transducer beam search (include/statecatcher.h, sc_rnnt_beam_*).  The state is a uint8
+// [B, bytes per stream] tensor of rnnt_beam_state_bytes(1, beam, max_symbols, max_frames) bytes
+// per stream.
+int64_t rnnt_beam_state_bytes(int64_t B, int64_t beam, int64_t max_symbols, int64_t max_frames) {
+  TORCH_CHECK(B >= 0 && B <= INT32_MAX && max_frames >= 0 && max_frames <= INT32_MAX,
+              "statecatcher::rnnt_beam_state_bytes: B or max_frames out of range");
+  const size_t n = sc_rnnt_beam_state_bytes((int)B, (int)beam, (int)max_symbols, (int)max_frames);
+  TORCH_CHECK(n != 0 || B == 0, "statecatcher::rnnt_beam_state_bytes: beam=", beam, " (1..32), "
+              "max_symbols=", max_symbols, " (1..8), max_frames=", max_frames,
+              " do not describe a state");
+  return (int64_t)n;
+}
+
+void rnnt_beam_reset_hip(Tensor& state, int64_t beam, int64_t max_symbols, int64_t max_frames,
+                         const optional<Tensor>& streams) {
+  c10::DeviceGuard guard(state.device());
+  const char* me = "statecatcher::rnnt_beam_reset_: ";
+  check_beam_state(state, me);
+  const int64_t B = state.size(0);
+  if (streams && streams->defined())
+    TORCH_CHECK(streams->scalar_type() == at::kFloat && streams->numel() == B &&
+                streams->is_contiguous(), me, "streams must be contiguous fp32 [B]");
+  sc_check(sc_rnnt_beam_reset(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
+                              (int)max_symbols, (int)max_frames, (const float*)opt_ptr(streams),
+                              stream_for(state)),
+           "statecatcher::rnnt_beam_reset_");
+}
+
+void rnnt_beam_reset_meta(Tensor& state, int64_t beam, int64_t max_symbols, int64_t max_frames,
+                          const optional<Tensor>& streams) {}
+
+void rnnt_beam_frames_hip(const Tensor& enc_in, const Tensor& pred_tab, const Tensor& W,
+                          const Tensor& bias, Tensor& state, const optional<Tensor>& lengths_in,
+                          const optional<Tensor>& mask, int64_t blank, int64_t beam, int64_t top_k,
+                          int64_t max_symbols) {
+  c10::DeviceGuard guard(enc_in.device());
+  const char* me = "statecatcher::rnnt_beam_frames_: ";
+  TORCH_CHECK(enc_in.dim() == 3 && pred_tab.dim() == 2 && W.dim() == 2 && bias.dim() == 1, me,
+              "enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]");
+  check_beam_state(state, me);
+  Tensor enc = enc_in.stride(2) == 1 || enc_in.numel() == 0 ? enc_in : enc_in.contiguous();
+  const int64_t B = enc.size(0), T = enc.size(1), J = enc.size(2), V = W.size(0);
+  TORCH_CHECK(W.size(1) == J && pred_tab.size(0) == V && pred_tab.size(1) == J && bias.numel() == V,
+              me, "pred_tab / W must be [V,J] and bias [V]");
+  TORCH_CHECK(pred_tab.scalar_type() == enc.scalar_type() && W.scalar_type() == enc.scalar_type(),
+              me, "enc_p, pred_tab and W must share one dtype");
+  TORCH_CHECK(state.size(0) == B, me, "the state holds ", state.size(0), " streams, enc_p has ", B);
+  Tensor pc = pred_tab.contiguous(), wc = W.contiguous(), bc = f32c(bias);
+  optional<Tensor> lens;
+  if (lengths_in && lengths_in->defined()) {
+    lens = lengths_in->to(at::kLong).contiguous();
+    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
+  }
+  int64_t mb = 0, mt = 0;
+  if (mask && mask->defined()) {
+    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
+                mask->size(1) == T, me, "mask must be fp32 [B,T]");
+    mb = mask->stride(0);
+    mt = mask->stride(1);
+  }
+  TORCH_CHECK(B <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, me, "shape out of range");
+  const size_t ws_bytes = sc_rnnt_beam_workspace_bytes((int)B, (int)V);
+  Tensor ws = at::empty({(int64_t)(ws_bytes ? ws_bytes : 4)}, enc.options().dtype(at::kByte));
+  sc_check(sc_rnnt_beam_frames(enc.data_ptr(), pc.data_ptr(), wc.data_ptr(), dtype_code(enc),
+                               (const float*)bc.data_ptr(), (int)B, (int)T, (int)V, (int)J,
+                               enc.stride(0), enc.stride(1), (const int64_t*)opt_ptr(lens),
+                               (const float*)opt_ptr(mask), mb, mt, (int)blank, (int)beam,
+                               (int)top_k, (int)max_symbols, state.data_ptr(),
+                               (size_t)state.numel(), ws.data_ptr(), (size_t)ws.numel(),
+                               stream_for(enc)),
+           "statecatcher::rnnt_beam_frames_");
+}
+
+void rnnt_beam_frames_meta(const Tensor& enc, const Tensor& pred_tab, const Tensor& W,
+                           const Tensor& bias, Tensor& state, const optional<Tensor>& lengths,
+                           const optional<Tensor>& mask, int64_t blank, int64_t beam, int64_t top_k,
+                           int64_t max_symbols) {
+  TORCH_CHECK(enc.dim() == 3 && W.dim() == 2 && W.size(1) == enc.size(2) && state.dim() == 2 &&
+                  state.size(0) == enc.size(0),
+              "statecatcher::rnnt_beam_frames_: enc_p [B,T,J], W [V,J], state [B, bytes per stream]");
+}
+
+// tokens, frames [B,nbest,cap] (-1 where nothing is written), lens, scores [B,nbest], status [B]
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rnnt_beam_result_hip(
+    const Tensor& state, int64_t beam, int64_t max_symbols, int64_t nbest, int64_t cap) {
+  c10::DeviceGuard guard(state.device());
+  const char* me = "statecatcher::rnnt_beam_result: ";
+  check_beam_state(state, me);
+  TORCH_CHECK(nbest >= 0 && nbest <= INT32_MAX && cap >= 0 && cap <= INT32_MAX, me,
+              "nbest or cap out of range");
+  const int64_t B = state.size(0);
+  auto io = state.options().dtype(at::kInt);
+  Tensor tokens = at::full({B, nbest, cap}, -1, io), frames = at::full({B, nbest, cap}, -1, io);
+  Tensor lens = at::empty({B, nbest}, io);
+  Tensor scores = at::empty({B, nbest}, state.options().dtype(at::kFloat));
+  Tensor status = at::empty({B}, io);
+  sc_check(sc_rnnt_beam_result(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
+                               (int)max_symbols, (int)nbest, (int32_t*)tokens.data_ptr(),
+                               (int32_t*)frames.data_ptr(), (int)cap, (int32_t*)lens.data_ptr(),
+                               (float*)scores.data_ptr(), (int32_t*)status.data_ptr(),
+                               stream_for(state)),
+           "statecatcher::rnnt_beam_result");
+  return {tokens, lens, scores, frames, status};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rnnt_beam_result_meta(
+    const Tensor& state, int64_t beam, int64_t max_symbols, int64_t nbest, int64_t cap) {
+  TORCH_CHECK(state.dim() == 2 && nbest >= 0 && cap >= 0,
+              "statecatcher::rnnt_beam_result: state [B, bytes per stream], nbest, cap >= 0");
+  const int64_t B = state.size(0);
+  auto io = state.options().dtype(at::kInt);
+  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
+          at::empty({B, nbest}, state.options().dtype(at::kFloat)), at::empty({B, nbest, cap}, io),
+          at::empty({B}, io)};
+}
+
+// offline: a fresh state for max_frames (default T) live frames, the frames, the result
+std::tuple<Tensor, Tensor, Tensor, Tensor> rnnt_beam_decode_hip(
+    const Tensor& enc, const Tensor& pred_tab, const Tensor& W, const Tensor& bias,
+    const optional<Tensor>& lengths, const optional<Tensor>& mask, int64_t blank, int64_t beam,
+    int64_t top_k, int64_t max_symbols, int64_t nbest, optional<int64_t> max_frames_in,
+    optional<int64_t> cap_in) {
+  c10::DeviceGuard guard(enc.device());
+  TORCH_CHECK(enc.dim() == 3, "statecatcher::rnnt_beam_decode: enc_p must be [B,T,J]");
+  const int64_t B = enc.size(0), max_frames = max_frames_in ? *max_frames_in : enc.size(1);
+  const int64_t per = rnnt_beam_state_bytes(1, beam, max_symbols, max_frames);
+  Tensor state = at::empty({B, per}, enc.options().dtype(at::kByte));
+  rnnt_beam_reset_hip(state, beam, max_symbols, max_frames, c10::nullopt);
+  rnnt_beam_frames_hip(enc, pred_tab, W, bias, state, lengths, mask, blank, beam, top_k,
+                       max_symbols);
+  auto r = rnnt_beam_result_hip(state, beam, max_symbols, nbest,
+                                cap_in ? *cap_in : max_frames * max_symbols);
+  return {std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> rnnt_beam_decode_meta(
+    const Tensor& enc, const Tensor& pred_tab, const Tensor& W, const Tensor& bias,
+    const optional<Tensor>& lengths, const optional<Tensor>& mask, int64_t blank, int64_t beam,
+    int64_t top_k, int64_t max_symbols, int64_t nbest, optional<int64_t> max_frames_in,
+    optional<int64_t> cap_in) {
+  TORCH_CHECK(enc.dim() == 3 && nbest >= 0, "statecatcher::rnnt_beam_decode: enc_p must be [B,T,J]");
+  const int64_t B = enc.size(0), max_frames = max_frames_in ? *max_frames_in : enc.size(1);
+  const int64_t cap = cap_in ? *cap_in : max_frames * max_symbols;
+  auto io = enc.options().dtype(at::kInt);
+  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
+          at::empty({B, nbest}, enc.options().dtype(at::kFloat)), at::empty({B, nbest, cap}, io)};
+}
+
 // ------------------------------------------------------------------------------ mLSTM --------
 // q, k [B,NH,T,DQ], v [B,NH,T,DV] (bf16 / f16, contiguous), igate / fgate fp32 [B,NH,T]: the
 // chunkwise cell of the xLSTM encoder (model.py:214-229; the fork's mlstm_kernels).
@@ -1009,6 +1158,19 @@ TORCH_LIBRARY(statecatcher, m) {
   m.def("ctc_beam_decode(Tensor x, Tensor? lengths=None, Tensor? mask=None, int blank=0, "
         "int beam=8, int top_k=8, int nbest=1, bool is_logits=False, int? max_frames=None, "
         "int? cap=None) -> (Tensor tokens, Tensor lens, Tensor scores)");
+  m.def("rnnt_beam_state_bytes(int B, int beam, int max_symbols, int max_frames) -> int",
+        &rnnt_beam_state_bytes);
+  m.def("rnnt_beam_reset_(Tensor(a!) state, int beam, int max_symbols, int max_frames, "
+        "Tensor? streams=None) -> ()");
+  m.def("rnnt_beam_frames_(Tensor enc_p, Tensor pred_tab, Tensor W, Tensor bias, Tensor(a!) state, "
+        "Tensor? lengths=None, Tensor? mask=None, int blank=0, int beam=8, int top_k=8, "
+        "int max_symbols=2) -> ()");
+  m.def("rnnt_beam_result(Tensor state, int beam, int max_symbols, int nbest=1, int cap=0)"
+        " -> (Tensor tokens, Tensor lens, Tensor scores, Tensor frames, Tensor status)");
+  m.def("rnnt_beam_decode(Tensor enc_p, Tensor pred_tab, Tensor W, Tensor bias, "
+        "Tensor? lengths=None, Tensor? mask=None, int blank=0, int beam=8, int top_k=8, "
+        "int max_symbols=2, int nbest=1, int? max_frames=None, int? cap=None)"
+        " -> (Tensor tokens, Tensor lens, Tensor scores, Tensor frames)");
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
@@ -1035,6 +1197,10 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("ctc_beam_frames_", &ctc_beam_frames_hip);
   m.impl("ctc_beam_result", &ctc_beam_result_hip);
   m.impl("ctc_beam_decode", &ctc_beam_decode_hip);
+  m.impl("rnnt_beam_reset_", &rnnt_beam_reset_hip);
+  m.impl("rnnt_beam_frames_", &rnnt_beam_frames_hip);
+  m.impl("rnnt_beam_result", &rnnt_beam_result_hip);
+  m.impl("rnnt_beam_decode", &rnnt_beam_decode_hip);
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
@@ -1061,4 +1227,8 @@ TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("ctc_beam_frames_", &ctc_beam_frames_meta);
   m.impl("ctc_beam_result", &ctc_beam_result_meta);
   m.impl("ctc_beam_decode", &ctc_beam_decode_meta);
+  m.impl("rnnt_beam_reset_", &rnnt_beam_reset_meta);
+  m.impl("rnnt_beam_frames_", &rnnt_beam_frames_meta);
+  m.impl("rnnt_beam_result", &rnnt_beam_result_meta);
+  m.impl("rnnt_beam_decode", &rnnt_beam_decode_meta);
 }

@@ -2,7 +2,7 @@
 and the transducer counterpart the reference does not have."""
 import torch
 
-from .ops import ctc_beam_decode, ctc_greedy_decode, rnnt_greedy_decode
+from .ops import ctc_beam_decode, ctc_greedy_decode, rnnt_beam_decode, rnnt_greedy_decode
 
 
 def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
@@ -67,3 +67,41 @@ def rnnt_greedy_decoder(enc_out, joiner, input_lengths, blank=0, max_symbols=4, 
     if n == 2:
         return toks
     return toks, [packed[b, 1 + cap:1 + cap + c].tolist() for b, c in enumerate(counts)]
+
+
+def rnnt_beam_decoder(enc_out, joiner, input_lengths, blank=0, beam=8, top_k=8, max_symbols=2,
+                      nbest=1, return_scores=False, return_frames=False):
+    """Transducer beam search of encoder output enc_out [B,T,D] with ``joiner`` (either joiner
+    class of model.py; ops.rnnt_beam_decode, fp32 arithmetic).  nbest=1 returns the List[List[int]]
+    of rnnt_greedy_decoder; nbest>1 a list per stream of up to nbest token lists, best first.
+    return_scores adds the log-probabilities and return_frames the live-frame index of every
+    token, each in the same nesting: (hyps[, scores][, frames]).  The cost of a frame grows with
+    max_symbols + 1 joint rounds, and a trained transducer of this project emits about 0.1 tokens
+    per frame, so max_symbols defaults to 2 (the greedy decoder's 4 buys nothing here).  enc_proj
+    and the predictor table (rnnt_joiner_tables) are computed once per call; one host copy at the
+    end."""
+    jm = getattr(joiner, "module", joiner)
+    with torch.no_grad():
+        enc_p = jm.enc_proj(enc_out)
+        pred_tab, W, bias = rnnt_joiner_tables(jm, enc_p.dtype)
+        out = rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths=input_lengths, blank=blank,
+                               beam=beam, top_k=top_k, max_symbols=max_symbols, nbest=nbest,
+                               return_frames=return_frames)
+    tokens, lens, scores = out[:3]
+    B, N, cap = tokens.shape
+    parts = [lens.unsqueeze(2), scores.view(torch.int32).unsqueeze(2), tokens] + list(out[3:])
+    packed = torch.cat(parts, 2).cpu()
+    lens, scores = packed[:, :, 0].tolist(), packed[:, :, 1].contiguous().view(torch.float32).tolist()
+    alive = [[n for n in range(N) if lens[b][n] >= 0] for b in range(B)]
+    hyps = [[packed[b, n, 2:2 + lens[b][n]].tolist() for n in alive[b]] for b in range(B)]
+    res = [hyps]
+    if return_scores:
+        res.append([[scores[b][n] for n in alive[b]] for b in range(B)])
+    if return_frames:
+        res.append([[packed[b, n, 2 + cap:2 + cap + lens[b][n]].tolist() for n in alive[b]]
+                    for b in range(B)])
+    if nbest == 1:
+        empty = [[], float("-inf"), []]
+        kinds = [0] + ([1] if return_scores else []) + ([2] if return_frames else [])
+        res = [[r[0] if r else empty[k] for r in part] for part, k in zip(res, kinds)]
+    return tuple(res) if len(res) > 1 else res[0]

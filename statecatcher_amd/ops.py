@@ -1507,6 +1507,172 @@ def ctc_beam_decode(log_probs_or_logits, lengths=None, mask=None, blank=0, beam=
     return ctc_beam_result(state, nbest, cap, out)
 
 
+class RnntBeamState:
+    """The state of B transducer beam search streams (include/statecatcher.h, sc_rnnt_beam_*):
+    ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its
+    status word and its token trie for ``max_frames`` live frames of at most ``max_symbols``
+    tokens.  Made reset; ``reset()`` starts every stream afresh, ``reset(streams)`` the listed
+    stream indices (or, given a fp32 [B] tensor, the streams whose entry is non-zero; no
+    allocation then)."""
+
+    def __init__(self, B, beam, max_symbols, max_frames, device):
+        lib = _lib.load()
+        B, beam, max_symbols, max_frames = int(B), int(beam), int(max_symbols), int(max_frames)
+        nbytes = lib.sc_rnnt_beam_state_bytes(max(B, 1), beam, max_symbols, max_frames)
+        if B < 0 or nbytes == 0:
+            raise ValueError(f"rnnt_beam_state: B={B}, beam={beam} (1..32), max_symbols="
+                             f"{max_symbols} (1..8), max_frames={max_frames} (>= 0, max_frames * "
+                             "max_symbols * beam < 2^31) do not describe a state")
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("statecatcher ops run only on a ROCm GPU (HIP); got device "
+                               f"{device}. There is no CPU fallback.")
+        self.B, self.beam, self.max_symbols, self.max_frames = B, beam, max_symbols, max_frames
+        self.buf = torch.zeros(B, nbytes // max(B, 1), dtype=torch.uint8, device=device)
+        self._ws = None
+        self.reset()
+
+    @property
+    def nbytes(self):
+        return self.buf.numel()
+
+    def reset(self, streams=None):
+        if streams is not None and not isinstance(streams, torch.Tensor):
+            m = torch.zeros(self.B, dtype=torch.float32)
+            m[list(streams)] = 1.0
+            streams = m.to(self.buf.device, non_blocking=True)
+        if streams is not None and (streams.dtype != torch.float32 or streams.numel() != self.B
+                                    or not streams.is_contiguous()):
+            raise ValueError("rnnt_beam_state.reset: streams must be contiguous fp32 [B]")
+        require_device(streams)
+        rc = _lib.load().sc_rnnt_beam_reset(ptr(self.buf), self.nbytes, self.B, self.beam,
+                                            self.max_symbols, self.max_frames, ptr(streams),
+                                            stream_of(self.buf))
+        check(rc, "sc_rnnt_beam_reset")
+
+    def workspace(self, nbytes):
+        """The walk's workspace, grown when a call needs more (kept between calls, so a chunk
+        call of a fixed shape allocates once)."""
+        if self._ws is None or self._ws.numel() < nbytes:
+            self._ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.buf.device)
+        return self._ws
+
+
+def rnnt_beam_state(B, beam, max_symbols, max_frames, device):
+    """A reset RnntBeamState for chunked rnnt_beam_decode: B streams, beam width ``beam``, at most
+    ``max_symbols`` tokens per frame, room for ``max_frames`` live frames per stream."""
+    return RnntBeamState(B, beam, max_symbols, max_frames, device)
+
+
+def rnnt_beam_result(state, nbest=1, cap=None, out=None, return_frames=False, return_status=False):
+    """The first ``nbest`` hypotheses of every stream of ``state`` (sc_rnnt_beam_result; the state
+    is not changed) -> (tokens int32 [B,nbest,cap], lens int32 [B,nbest], scores fp32 [B,nbest]
+    [, frames int32 [B,nbest,cap]][, status int32 [B]]).  The first min(lens, cap) entries of
+    tokens[b,n] (and frames[b,n]: the ordinal, counted since reset, of the live frame that emitted
+    the token) are valid and the rest is -1; lens is the full token count; a rank with no
+    hypothesis has lens -1 and score -inf.  cap defaults to max_frames * max_symbols, which cannot
+    overflow.  out = (tokens, lens, scores[, frames]): write into these instead of allocating
+    (they are not filled then).  status bit 0: the stream met more than max_frames live frames
+    and ignored the rest."""
+    B, nbest = state.B, int(nbest)
+    dev = state.buf.device
+    frames = None
+    if out is not None:
+        tokens, lens, scores = out[:3]
+        frames = out[3] if len(out) > 3 else None
+        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 3 \
+            and tuple(tokens.shape[:2]) == (B, nbest) and lens.dtype == torch.int32 \
+            and lens.is_contiguous() and tuple(lens.shape) == (B, nbest) \
+            and scores.dtype == torch.float32 and scores.is_contiguous() \
+            and tuple(scores.shape) == (B, nbest) \
+            and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous()
+                                    and frames.shape == tokens.shape))
+        if not ok:
+            raise ValueError("rnnt_beam_result: out = (tokens int32 [B,nbest,cap], lens int32 "
+                             "[B,nbest], scores fp32 [B,nbest][, frames as tokens]), contiguous")
+        require_device(tokens, lens, scores, frames)
+        cap = tokens.shape[2]
+        return_frames = frames is not None
+    else:
+        cap = state.max_frames * state.max_symbols if cap is None else int(cap)
+        if cap < 0 or nbest < 0:
+            raise ValueError(f"rnnt_beam_result: cap={cap} or nbest={nbest} is negative")
+        tokens = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+        if return_frames:
+            frames = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    rc = _lib.load().sc_rnnt_beam_result(ptr(state.buf), state.nbytes, B, state.beam,
+                                         state.max_symbols, nbest, ptr(tokens), ptr(frames), cap,
+                                         ptr(lens), ptr(scores), ptr(status), stream_of(state.buf))
+    check(rc, "sc_rnnt_beam_result")
+    res = (tokens, lens, scores)
+    if return_frames:
+        res += (frames,)
+    if return_status:
+        res += (status,)
+    return res
+
+
+def rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, beam=8, top_k=8,
+                     max_symbols=2, nbest=1, cap=None, state=None, out=None, return_frames=False,
+                     max_frames=None):
+    """Transducer beam search of a stateless-predictor joiner (sc_rnnt_beam_*, csrc/rnnt_beam.hip;
+    the contract is in include/statecatcher.h).  Inputs as rnnt_greedy_decode: enc_p [B,T,J]
+    (unit inner stride, any other strides), pred_tab [V,J], W [V,J] of one dtype (fp32 / bf16 /
+    f16), bias fp32 [V]; lengths int64 [B] (tensor or list) and mask fp32 [B,T] (0 = dead frame)
+    are optional.  Every frame lets each hypothesis take a blank or up to ``max_symbols`` of its
+    ``top_k`` likeliest tokens and keeps the ``beam`` best; all arithmetic is fp32.
+
+    state=None decodes offline: a fresh state with room for max_frames (default T) live frames,
+    the frames, the result.  With a ``rnnt_beam_state`` the call consumes enc_p as the next chunk
+    of every stream (the state's own beam and max_symbols are used) and returns the result so far;
+    a stream fed in chunks gives exactly the result of the stream fed whole.
+
+    Returns rnnt_beam_result(state, nbest, cap, out, return_frames): (tokens int32 [B,nbest,cap],
+    lens int32 [B,nbest], scores fp32 [B,nbest][, frames]), hypotheses best first.  With a state
+    and out= the call allocates nothing once the state's workspace has its size (safe inside a
+    hipGraph capture).  No host sync (a ``lengths`` list is copied to the device
+    asynchronously)."""
+    require_device(enc_p, pred_tab, W, bias, mask)
+    if enc_p.dim() != 3 or pred_tab.dim() != 2 or W.dim() != 2 or bias.dim() != 1:
+        raise ValueError("rnnt_beam_decode: enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]")
+    B, T, J = enc_p.shape
+    V = W.shape[0]
+    if tuple(W.shape) != (V, J) or tuple(pred_tab.shape) != (V, J) or bias.numel() != V:
+        raise ValueError(f"rnnt_beam_decode: pred_tab / W must be [V,J]=[{V},{J}] and bias [V], "
+                         f"got {tuple(pred_tab.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}")
+    if pred_tab.dtype != enc_p.dtype or W.dtype != enc_p.dtype:
+        raise ValueError("rnnt_beam_decode: enc_p, pred_tab and W must share one dtype")
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError("rnnt_beam_decode: bias must be contiguous fp32 [V]")
+    if (T > 0 and B > 0 and enc_p.stride(2) != 1) or not pred_tab.is_contiguous() \
+            or not W.is_contiguous():
+        raise ValueError("rnnt_beam_decode: enc_p needs unit inner stride, pred_tab / W contiguous")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
+        raise ValueError("rnnt_beam_decode: mask must be fp32 [B, T]")
+    lens = None if lengths is None else _as_len_tensor(lengths, enc_p.device)
+    if lens is not None and lens.numel() != B:
+        raise ValueError("rnnt_beam_decode: lengths must have B entries")
+    if state is None:
+        state = RnntBeamState(B, beam, max_symbols, T if max_frames is None else max_frames,
+                              enc_p.device)
+    elif state.B != B or state.buf.device != enc_p.device:
+        raise ValueError(f"rnnt_beam_decode: the state holds {state.B} streams on "
+                         f"{state.buf.device}, enc_p has {B} on {enc_p.device}")
+    lib = _lib.load()
+    ws = state.workspace(lib.sc_rnnt_beam_workspace_bytes(B, V))
+    rc = lib.sc_rnnt_beam_frames(
+        ptr(enc_p), ptr(pred_tab), ptr(W), dtype_code(enc_p), ptr(bias), B, T, V, J,
+        enc_p.stride(0), enc_p.stride(1), ptr(lens), ptr(mask),
+        mask.stride(0) if mask is not None else 0, mask.stride(1) if mask is not None else 0,
+        int(blank), state.beam, int(top_k), state.max_symbols, ptr(state.buf), state.nbytes,
+        ptr(ws), ws.numel(), stream_of(enc_p))
+    check(rc, "sc_rnnt_beam_frames")
+    return rnnt_beam_result(state, nbest, cap, out, return_frames)
+
+
 # ------------------------------------------------------------------- feature frontend --------
 def fbank(audio, kind="mfcc", sample_rate=16000):
     """make_frontend(kind)(audio).transpose(-1, -2) on the GPU (fbank.hip): audio fp32

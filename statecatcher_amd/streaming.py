@@ -43,6 +43,9 @@ transducer decode instead (the reference has none): enc_p = joiner.enc_proj(logi
 block's K frames (lucy_frame_gemm on the frame engine, addmm on the library engine), then ONE
 sc_rnnt_greedy_decode launch (csrc/rnnt_decode.hip) with each stream's last emitted token carried
 in ``prev`` (``blank`` at stream start, compute_loss's predictor prefix), inside the same graph.
+With ``beam`` as well the block ends in the transducer beam search instead (csrc/rnnt_beam.hip):
+one sc_rnnt_beam_frames launch on a persistent state plus one result launch, and step() returns
+the current n-best of every stream since its reset.
 
 StreamingLucyRNNtriton streams a LucyRNNtriton (lucyrnn_triton.py, the encoder the training step
 runs) the same way.  Its cell normalises per element, so a layer of a frame is ONE launch
@@ -68,8 +71,9 @@ class _StreamBase:
     _frame(j) and _block_wavefront()."""
 
     joiner = False   # True on an instance built with a joiner: the block ends in the transducer decode
+    beam = None      # the beam width on an instance built with a joiner and beam=
 
-    def _init_joiner(self, joiner, max_symbols, dev):
+    def _init_joiner(self, joiner, max_symbols, dev, beam=None, top_k=8, nbest=1, max_frames=4096):
         """Snapshot the joiner: enc_proj for the block's projection, the [V, J] predictor table
         and the output projection for the decode (fp32 on the frame engine, whose activations
         are fp32; ``dtype`` on the library engine), and the static decode outputs."""
@@ -94,6 +98,19 @@ class _StreamBase:
         self.tokens = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
         self.tok_frames = torch.full((B, cap), -1, dtype=torch.int32, device=dev)
         self.counts = torch.zeros(B, dtype=torch.int32, device=dev)
+        if beam is not None:
+            # the beam search's persistent state (room for max_frames live frames per stream
+            # between resets) and the static n-best buffers step() hands back
+            self.beam, self.top_k, self.nbest = int(beam), int(top_k), int(nbest)
+            if not 1 <= self.nbest <= self.beam:
+                raise ValueError("nbest must be in [1, beam]")
+            if not 1 <= self.top_k <= 32:
+                raise ValueError("top_k must be in [1, 32]")
+            self.beam_state = ops.rnnt_beam_state(B, self.beam, self.max_symbols, max_frames, dev)
+            cap = int(max_frames) * self.max_symbols
+            self.beam_tokens = torch.full((B, self.nbest, cap), -1, dtype=torch.int32, device=dev)
+            self.beam_lens = torch.zeros(B, self.nbest, dtype=torch.int32, device=dev)
+            self.beam_scores = torch.zeros(B, self.nbest, dtype=torch.float32, device=dev)
 
     def _rnnt_block(self):
         """enc_proj over the block's K frames of logits, then one greedy transducer launch."""
@@ -103,6 +120,12 @@ class _StreamBase:
             ops.lucy_frame_gemm(ops.FRAME_PLAIN, lg, self.w_enc, self.b_enc, ep)
         else:
             torch.addmm(self.b_enc, lg, self.w_enc.t(), out=ep)
+        if self.beam is not None:
+            ops.rnnt_beam_decode(self.enc_p.transpose(0, 1), self.pred_tab, self.w_join,
+                                 self.b_join, mask=self.mask.t(), blank=self.blank,
+                                 top_k=self.top_k, nbest=self.nbest, state=self.beam_state,
+                                 out=(self.beam_tokens, self.beam_lens, self.beam_scores))
+            return
         ops.rnnt_greedy_decode(self.enc_p.transpose(0, 1), self.pred_tab, self.w_join, self.b_join,
                                mask=self.mask.t(), blank=self.blank, max_symbols=self.max_symbols,
                                prev=self.prev, out=(self.tokens, self.counts, self.tok_frames))
@@ -139,6 +162,8 @@ class _StreamBase:
                 else:
                     buf[idx] = src.to(buf.device, torch.float32)[idx]
         self.prev[idx] = self.blank if self.joiner else -1
+        if self.beam is not None:
+            self.beam_state.reset(None if streams is None else torch.as_tensor(streams).tolist())
 
     def state(self):
         """(h list, s list) fp32 copies — the reference's (h, s) return (lucyrnn.py:188-189)."""
@@ -155,7 +180,10 @@ class _StreamBase:
         The logits of the block stay in ``self.logits`` ([K, B, V]).
         With a joiner: returns (tokens int32 [B, K * max_symbols], frames, counts int32 [B]) on
         the device instead: row b's first counts[b] tokens are this block's emissions, frames
-        their frame index within the block; later entries are stale."""
+        their frame index within the block; later entries are stale.
+        With a joiner and beam: returns (tokens int32 [B, nbest, max_frames * max_symbols], lens
+        int32 [B, nbest], scores fp32 [B, nbest]): the current n-best of every stream since its
+        reset, best first (ops.rnnt_beam_result's layout; entries past lens are stale)."""
         self._x_in().copy_(x.transpose(0, 1))
         if mask is None:
             self.mask.fill_(1.0)
@@ -165,6 +193,8 @@ class _StreamBase:
             self.graph.replay()
         else:
             self._block()
+        if self.beam is not None:
+            return self.beam_tokens, self.beam_lens, self.beam_scores
         if self.joiner:
             return self.tokens, self.tok_frames, self.counts
         return self.emit.t()
@@ -173,7 +203,8 @@ class _StreamBase:
         """Whole utterances through the streaming path: feats [B, T, input_dim] raw frames,
         stacked as the model does (lucyrnn.py:92-99: the tail T % stack_order is dropped, a
         stacked frame is live when all its frames are).  Returns the decoder.py token lists
-        (and logits [B, T', V] if asked).  One host sync at the end."""
+        (and logits [B, T', V] if asked).  One host sync at the end.  With beam: the best
+        hypothesis of every stream since its reset."""
         B, T, F = feats.shape
         k = self.cfg.stack_order
         Tt = T - T % k
@@ -189,7 +220,9 @@ class _StreamBase:
             xb[:, :n] = x[:, t0:t0 + n]
             mb = torch.zeros(B, self.K, device=self.x.device)   # padding frames are masked out
             mb[:, :n] = 1.0 if m is None else m[:, t0:t0 + n]
-            if self.joiner:
+            if self.beam is not None:
+                self.step(xb, mb)
+            elif self.joiner:
                 tk, _, ct = self.step(xb, mb)
                 emits.append(torch.cat([ct.unsqueeze(1), tk], 1))   # (a copy: count, tokens)
             else:
@@ -197,7 +230,11 @@ class _StreamBase:
             if return_logits:
                 logits.append(self.logits[:n].transpose(0, 1).clone())
         em = torch.cat(emits, 1).cpu() if emits else torch.zeros(B, 0, dtype=torch.int32)
-        if self.joiner:
+        if self.beam is not None:
+            ln = self.beam_lens[:, 0].clamp(min=0)
+            best = self.beam_tokens[:, 0, :max(int(ln.max()), 1)].cpu()
+            toks = [best[b, :n].tolist() for b, n in enumerate(ln.tolist())]
+        elif self.joiner:
             w = 1 + self.K * self.max_symbols
             toks = [[t for k in range(0, em.shape[1], w) for t in row[k + 1:k + 1 + row[k]]]
                     for row in em.tolist()]
@@ -216,11 +253,16 @@ class StreamingLucyRNN(_StreamBase):
     throughput); state is fp32 either way.  graph: capture the block as a hipGraph.
     joiner: decode as a transducer with this joiner (at most ``max_symbols`` tokens per frame)
     instead of greedy CTC; its weights are snapshotted too.
+    beam (with a joiner): transducer beam search of this width instead of the greedy decode, each
+    hypothesis extended by its ``top_k`` likeliest tokens (max_symbols 1..8 then); step() returns
+    the ``nbest`` best hypotheses since the stream's reset, which may span ``max_frames`` live
+    frames.
     """
 
     def __init__(self, model: LucyRNN, batch: int, frames_per_call: int = 1,
                  dtype=torch.float32, blank: int = 0, graph: bool = True, engine: str = "auto",
-                 schedule: str = "wavefront", joiner=None, max_symbols: int = 4):
+                 schedule: str = "wavefront", joiner=None, max_symbols: int = 4, beam=None,
+                 top_k: int = 8, nbest: int = 1, max_frames: int = 4096):
         cfg = model.config
         dev = next(model.parameters()).device
         ops._lib.require_device(next(model.parameters()))
@@ -261,8 +303,10 @@ class StreamingLucyRNN(_StreamBase):
         # wavefront: the frame engine's block as stages over (frame, layer) (_block_wavefront)
         self.schedule = schedule if engine == "frame" else "frame"
         self.joiner = joiner is not None
+        if beam is not None and not self.joiner:
+            raise ValueError("beam= needs a joiner (the beam search is the transducer's)")
         if self.joiner:
-            self._init_joiner(joiner, max_symbols, dev)
+            self._init_joiner(joiner, max_symbols, dev, beam, top_k, nbest, max_frames)
         z = lambda *s, dt=dtype: torch.zeros(*s, dtype=dt, device=dev)   # noqa: E731
         if engine == "frame":
             f32 = torch.float32
@@ -458,7 +502,8 @@ class StreamingLucyRNNtriton(_StreamBase):
 
     def __init__(self, model, batch: int, frames_per_call: int = 1, dtype=torch.float32,
                  blank: int = 0, graph: bool = True, schedule: str = "wavefront", joiner=None,
-                 max_symbols: int = 4):
+                 max_symbols: int = 4, beam=None, top_k: int = 8, nbest: int = 1,
+                 max_frames: int = 4096):
         from .lucyrnn_triton import LucyRNNtriton
         alt = ("; use LucyRNNtriton.forward(x, hidden_states) on chunks with carried state "
                "instead")
@@ -505,8 +550,10 @@ class StreamingLucyRNNtriton(_StreamBase):
         ob = model.output_proj.bias
         self.b_out = fb(ob) if ob is not None else torch.zeros(self.V, dtype=f32, device=dev)
         self.joiner = joiner is not None
+        if beam is not None and not self.joiner:
+            raise ValueError("beam= needs a joiner (the beam search is the transducer's)")
         if self.joiner:
-            self._init_joiner(joiner, max_symbols, dev)
+            self._init_joiner(joiner, max_symbols, dev, beam, top_k, nbest, max_frames)
         z = lambda *s: torch.zeros(*s, dtype=f32, device=dev)   # noqa: E731
         self.x = z(K, B, self.Dp)
         self.mask = torch.ones(K, B, dtype=f32, device=dev)

@@ -22,6 +22,7 @@ Reference interfaces (what a ``train.py`` user swaps in):
   clip_adam_  <- clip_grad_norm_(params, 50) + optim.Adam/AdamW.step() train.py:543-552
   rnnt_greedy_decode <- (absent in the reference) greedy decode of RNNTPredictorJoiner, model.py:112-145
   ctc_beam_decode <- (absent in the reference: decoder.py is greedy only) CTC prefix beam search
+  rnnt_beam_decode <- (absent in the reference) transducer beam search of RNNTPredictorJoiner
 """
 import os
 
@@ -32,7 +33,9 @@ OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay
        "layer_norm_fwd", "layer_norm_bwd", "ctc_fwd", "ctc_bwd", "ctc_mean", "ctc_greedy_decode",
        "mlstm_fwd", "mlstm_bwd", "mlstm_gate_bwd", "rnnt_joint_fwd", "rnnt_joint_bwd",
        "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode", "ctc_beam_state_bytes",
-       "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode")
+       "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode",
+       "rnnt_beam_state_bytes", "rnnt_beam_reset_", "rnnt_beam_frames_", "rnnt_beam_result",
+       "rnnt_beam_decode")
 
 _LOADED = False
 
@@ -278,6 +281,45 @@ def ctc_beam_frames_(x, state, lengths=None, mask=None, blank=0, beam=8, top_k=8
 def ctc_beam_result(state, beam, nbest=1, cap=0):
     """(tokens [B,nbest,cap], lens [B,nbest], scores [B,nbest], status [B]) of a state."""
     return load().ctc_beam_result(state, beam, nbest, cap)
+
+
+def rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, beam=8, top_k=8,
+                     max_symbols=2, nbest=1, max_frames=None, cap=None, return_frames=False):
+    """(tokens int32 [B,nbest,cap], lens int32 [B,nbest], scores fp32 [B,nbest][, frames]) of the
+    offline transducer beam search (ops.rnnt_beam_decode with state=None)."""
+    tok, lens, scores, frames = load().rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths, mask,
+                                                        blank, beam, top_k, max_symbols, nbest,
+                                                        max_frames, cap)
+    return (tok, lens, scores, frames) if return_frames else (tok, lens, scores)
+
+
+def rnnt_beam_state(B, beam, max_symbols, max_frames, device):
+    """A reset state tensor (uint8 [B, bytes per stream]) for rnnt_beam_frames_ / rnnt_beam_result."""
+    sc = load()
+    state = torch.zeros(B, sc.rnnt_beam_state_bytes(1, beam, max_symbols, max_frames),
+                        dtype=torch.uint8, device=device)
+    sc.rnnt_beam_reset_(state, beam, max_symbols, max_frames)
+    return state
+
+
+def rnnt_beam_reset_(state, beam, max_symbols, max_frames, streams=None):
+    """Every stream of ``state`` (or those with a non-zero entry in streams fp32 [B]) afresh."""
+    load().rnnt_beam_reset_(state, beam, max_symbols, max_frames, streams)
+    return state
+
+
+def rnnt_beam_frames_(enc_p, pred_tab, W, bias, state, lengths=None, mask=None, blank=0, beam=8,
+                      top_k=8, max_symbols=2):
+    """Consume enc_p [B,T,J] as the next chunk of every stream of ``state``, in place."""
+    load().rnnt_beam_frames_(enc_p, pred_tab, W, bias, state, lengths, mask, blank, beam, top_k,
+                             max_symbols)
+    return state
+
+
+def rnnt_beam_result(state, beam, max_symbols, nbest=1, cap=0):
+    """(tokens [B,nbest,cap], lens [B,nbest], scores [B,nbest], frames [B,nbest,cap], status [B])
+    of a state."""
+    return load().rnnt_beam_result(state, beam, max_symbols, nbest, cap)
 
 
 def gemm_tn(a, b, tile_m=0):
