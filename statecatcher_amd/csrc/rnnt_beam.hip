@@ -4,10 +4,11 @@
 // sc_rnnt_greedy_decode follows one path and returns no score.  This is the time-synchronous beam
 // search over the same joint: a hypothesis is a token prefix and one score, the predictor being a
 // [V, J] table of the last token.  All arithmetic is fp32; inputs are widened on load; z = tanh(..)
-// has the greedy kernel's form; lp = logit - logsumexp(logit); lae as in ctc_beam.hip.
+// has the greedy kernel's form; lp = logit - logsumexp(logit).  The state, its reset and result
+// kernels, the rankings' order, the top_k rounds and the list-and-rank step are beam_common.h's,
+// shared with ctc_beam.hip.
 //
-// Three kernels:
-//   rbeam_reset_kernel   the whole state or the selected streams back to [(empty, 0)]
+// The kernel of this file:
 //   rbeam_walk_kernel    one persistent workgroup of 1024 threads per stream consumes the call's
 //                        frames.  Per live frame, for r = 0 .. max_symbols, with C the round's
 //                        hypotheses (the beam when r = 0):
@@ -15,170 +16,35 @@
 //                          in passes of 16 hypotheses: every lane forms its row's logit for each
 //                          (FAST: the row of W in registers) -> image [16][V] | barrier | wave w:
 //                          max, sum of exponentials, lp[blank] and the top_k rounds of hypothesis
-//                          w of the pass (as ctc_beam.hip's beam_rows_kernel) | barrier |
+//                          w of the pass | barrier |
 //                          wave 0: blank steps into A (merge by (hash, length), else append in
 //                          order) and a floor under the beam-th largest extension | barrier |
-//                          extensions at or above the floor -> key list | barrier | rank by
-//                          counting, the first `beam` ranks are the next C and get trie nodes.
-//                        Then the `beam` largest of A are the new beam.  Every branch is
-//                        workgroup-uniform; every loop is bounded by T, max_symbols, beam, top_k,
-//                        V or J; nothing waits on another workgroup; nothing is allocated or
-//                        counted atomically in memory.
+//                          list and rank the extensions: the first `beam` ranks are the next C
+//                          and get trie nodes.
+//                        Then A is listed and ranked: its `beam` largest are the new beam.  Every
+//                        branch is workgroup-uniform; every loop is bounded by T, max_symbols,
+//                        beam, top_k, V or J; nothing waits on another workgroup; nothing is
+//                        allocated or counted atomically in memory.  The opaque() copy of tid at
+//                        the head of each phase (list_and_rank takes its own) keeps the fast path
+//                        under 128 VGPRs: leave them where they are.
 //     <DT, true>   J = 64, V <= 1024, W 16-byte aligned: lane v keeps row v of W in registers,
 //                  the image lives in LDS (64 KB dynamic) and a wave's row statistics keep each
 //                  lane's 16 elements of the row in registers through the top_k rounds
 //     <DT, false>  any V, J <= 256: rows of W are read from memory and the image lives in the
 //                  workspace (correct, not tuned)
-//   rbeam_result_kernel  one lane per (stream, hypothesis) walks the parent pointers
 //
-// Token history is a parent-pointer trie in the state: node 0 is the empty prefix, the candidate
-// kept at rank k of round r of live frame f is node 1 + (f * max_symbols + r) * beam + k =
-// (parent node, token), so nothing is counted in memory and a token's frame is read off its node.
-#include "sc_common.h"
+// The candidate kept at rank k of round r of live frame f is trie node
+// 1 + (f * max_symbols + r) * beam + k, so nothing is counted in memory and a token's frame is
+// read off its node.
+#include "beam_common.h"
 
 namespace sc {
 namespace rbeam {
 
-constexpr int kBeamMax = 32, kTopkMax = 32, kSymMax = 8;
 constexpr int kAMax = kBeamMax * (kSymMax + 1);   // entries of one frame's A
 constexpr int kThreads = 1024, kMaxJ = 256;
 constexpr int kRows = 16;                         // hypotheses of one pass: one per wave
-constexpr int kRankAll = 128;                     // up to this many extensions are ranked without a floor
-constexpr int kNoTok = -1;
-constexpr float kNegInf = -__builtin_huge_valf();
-
-// ------------------------------------------------------------------ state layout -------------
-// per stream, 8-byte aligned:
-//   int32  hdr[4]       live frames consumed, status, hypotheses alive, beam | max_symbols << 8
-//   uint64 hash[beam];  float score[beam];  int32 node[beam], len[beam], last[beam]
-//   int32  trie[1 + max_frames * max_symbols * beam][2]   (parent, token)
-struct Layout {
-  size_t hdr, stream;
-  int64_t max_frames;
-};
-static size_t hdr_bytes(int beam) { return (size_t)16 + 24 * (size_t)beam; }
-static size_t stream_bytes(int beam, int ms, int64_t max_frames) {
-  return hdr_bytes(beam) + 8 * (1 + (size_t)max_frames * ms * beam);
-}
-static Layout layout(size_t state_bytes, int B, int beam, int ms) {
-  Layout L{hdr_bytes(beam), 0, -1};
-  if (B <= 0 || state_bytes % (size_t)B) return L;
-  L.stream = state_bytes / (size_t)B;
-  const size_t per = 8 * (size_t)beam * ms;
-  if (L.stream < L.hdr + 8 || (L.stream - L.hdr - 8) % per) return L;
-  const size_t mf = (L.stream - L.hdr - 8) / per;
-  if (mf * (size_t)beam * ms < (size_t)0x7ffffff0) L.max_frames = (int64_t)mf;
-  return L;
-}
-
-struct View {
-  int32_t* hdr;
-  uint64_t* hash;
-  float* score;
-  int32_t *node, *len, *last, *trie;
-};
-__device__ __forceinline__ View view(void* state, size_t stream, size_t hdr, int b, int beam) {
-  char* p = (char*)state + (size_t)b * stream;
-  View v;
-  v.hdr = (int32_t*)p;
-  v.hash = (uint64_t*)(p + 16);
-  v.score = (float*)(p + 16 + 8 * (size_t)beam);
-  v.node = (int32_t*)(v.score + beam);
-  v.len = v.node + beam;
-  v.last = v.len + beam;
-  v.trie = (int32_t*)(p + hdr);
-  return v;
-}
-
-// ctc_beam.hip's helpers, unchanged
-__device__ __forceinline__ float lae(float a, float b) {
-  if (a == kNegInf) return b;
-  if (b == kNegInf) return a;
-  return fmaxf(a, b) + log1pf(expf(-fabsf(a - b)));
-}
-__device__ __forceinline__ uint64_t hash_push(uint64_t h, int c) {
-  h = (h ^ (uint64_t)(uint32_t)(c + 1)) * 0x9E3779B97F4A7C15ull;
-  return h ^ (h >> 32);
-}
-__device__ __forceinline__ float rank_key(float v) { return v != v ? kNegInf : v; }
-__device__ __forceinline__ bool key_beats(float ka, int ia, float kb, int ib) {
-  return (ka > kb) | ((ka == kb) & (ia < ib));
-}
-__device__ __forceinline__ uint64_t cand_key(float tot, int c) {
-  uint32_t u = __float_as_uint(tot + 0.0f);   // -0 -> +0
-  u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-  return ((uint64_t)u << 32) | (uint64_t)(0xffffffffu - (uint32_t)c);
-}
-// (key, index) argmax of a wave on DPP, as rnnt_decode.hip's row_argmax but in key_beats' order:
-// one exchange inside a row of 16 lanes (every lane has a partner), keeping the winner
-template <int CTRL>
-__device__ __forceinline__ void kmax_dpp(float& k, int& i) {
-  const float ok = __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(k), __float_as_int(k), CTRL, 0xf, 0xf, false));
-  const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false);
-  const bool take = key_beats(ok, oi, k, i);
-  k = take ? ok : k;
-  i = take ? oi : i;
-}
-// after this every lane holds the wave's winner (the order is total: any reduction tree agrees)
-__device__ __forceinline__ void wave_kmax(float& k, int& i) {
-  kmax_dpp<0xB1>(k, i);    // quad_perm [1,0,3,2]
-  kmax_dpp<0x4E>(k, i);    // quad_perm [2,3,0,1]
-  kmax_dpp<0x141>(k, i);   // row_half_mirror
-  kmax_dpp<0x140>(k, i);   // row_mirror: every lane of a row holds its row's winner
-  float wk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k), 0));
-  int wi = __builtin_amdgcn_readlane(i, 0);
-#pragma unroll
-  for (int r = 16; r < 64; r += 16) {
-    const float ok = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k), r));
-    const int oi = __builtin_amdgcn_readlane(i, r);
-    const bool take = key_beats(ok, oi, wk, wi);
-    wk = take ? ok : wk;
-    wi = take ? oi : wi;
-  }
-  k = wk;
-  i = wi;
-}
-// An opaque copy of a lane-varying value.  What a phase of the walk derives from its own copy
-// (lane masks, LDS addresses) cannot be computed once before the frame loop and kept alive across
-// the dot products, where the row of W leaves 64 registers for everything else.
-__device__ __forceinline__ int opaque(int x) {
-  asm volatile("" : "+v"(x));
-  return x;
-}
-// rnnt_decode.hip's tanh: expf form, ~1e-7 absolute; NaN stays NaN
-__device__ __forceinline__ float dec_tanh(float x) {
-  return 1.0f - 2.0f * rcp(exp2_(2.0f * kLog2e * x) + 1.0f);
-}
-
-// ------------------------------------------------------------------ reset --------------------
-struct ResetArgs {
-  void* state;
-  size_t stream, hdr;
-  int B, beam, ms;
-  const float* streams;
-};
-
-__global__ void __launch_bounds__(64) rbeam_reset_kernel(ResetArgs a) {
-  const int b = blockIdx.x, i = threadIdx.x;
-  if (a.streams && a.streams[b] == 0.0f) return;
-  const View s = view(a.state, a.stream, a.hdr, b, a.beam);
-  if (i < a.beam) {   // entry 0: the empty prefix; the rest: dead
-    s.hash[i] = 0;
-    s.score[i] = i == 0 ? 0.0f : kNegInf;
-    s.node[i] = 0;
-    s.len[i] = 0;
-    s.last[i] = kNoTok;
-  }
-  if (i == 0) {
-    s.hdr[0] = 0;
-    s.hdr[1] = 0;
-    s.hdr[2] = 1;
-    s.hdr[3] = a.beam | (a.ms << 8);
-    s.trie[0] = -1;
-    s.trie[1] = kNoTok;
-  }
-}
+constexpr int kNS = 1;                            // score floats of a state entry
 
 // ------------------------------------------------------------------ walk ---------------------
 struct WalkArgs {
@@ -226,8 +92,8 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
   __shared__ float theta;
   const int b = blockIdx.x, tid = threadIdx.x;
   const int J = FAST ? 64 : a.J, V = a.V, Bm = a.beam, K = a.top_k, MS = a.ms;
-  const View s = view(a.state, a.stream, a.hdr, b, Bm);
-  if (s.hdr[3] != (Bm | (MS << 8))) {   // not a state of this shape: touch nothing else
+  const BeamView s = beam_view<kNS>(a.state, a.stream, a.hdr, b, Bm);
+  if (s.hdr[3] != beam_tag(Bm, MS)) {   // not a state of this shape: touch nothing else
     if (tid == 0) s.hdr[1] |= 2;
     return;
   }
@@ -344,6 +210,14 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
           const int lane = ts & 63, wv = ts >> 6;
           const int i = r0 + wv;
           const float* row = img + (size_t)wv * V;
+          float lse;
+          const auto kmax = [](float& k, int& v) { wave_argmax<key_beats>(k, v); };
+          const auto emit = [&](int j, int bi) {
+            if (lane == 0) {
+              tk_idx[i][j] = bi;
+              tk_lp[i][j] = row[bi] - lse;
+            }
+          };
           if constexpr (FAST) {
             // V <= 1024: the lane's 16 elements of the row stay in registers from here on, so the
             // top_k rounds are compares on registers instead of dependent LDS reads
@@ -360,33 +234,12 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
 #pragma unroll
             for (int q = 0; q < 16; ++q) sm += lane + 64 * q < V ? expf(rv[q] - mx) : 0.0f;
             sm = wave_sum_dpp(sm);
-            const float lse = mx + logf(sm);
+            lse = mx + logf(sm);
             if (lane == 0) lpb[i] = row[a.blank] - lse;
             if (expand) {
 #pragma unroll
               for (int q = 0; q < 16; ++q) rv[q] = rank_key(rv[q] - lse);
-              float pk = __builtin_huge_valf();
-              int pi = -1;
-              for (int j = 0; j < K; ++j) {
-                float bk = kNegInf;
-                int bi = 0x7fffffff;
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                  const int v = lane + 64 * q;
-                  const bool after = key_beats(pk, pi, rv[q], v), best = key_beats(rv[q], v, bk, bi);
-                  const bool take = after & best & (v < V) & (v != a.blank);
-                  bk = take ? rv[q] : bk;
-                  bi = take ? v : bi;
-                }
-                wave_kmax(bk, bi);
-                bi = min(bi, V - 1);
-                if (lane == 0) {
-                  tk_idx[i][j] = bi;
-                  tk_lp[i][j] = row[bi] - lse;
-                }
-                pk = bk;
-                pi = bi;
-              }
+              topk_rounds_regs(K, V, a.blank, lane, rv, kmax, emit);
             }
           } else {
             float mx = kNegInf;
@@ -395,34 +248,11 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
             float sm = 0.0f;
             for (int v = lane; v < V; v += 64) sm += expf(row[v] - mx);
             sm = wave_sum_dpp(sm);
-            const float lse = mx + logf(sm);
+            lse = mx + logf(sm);
             if (lane == 0) lpb[i] = row[a.blank] - lse;
-            if (expand) {
-              // top_k rounds: the best non-blank element strictly after the previous round's winner
-              float pk = __builtin_huge_valf();
-              int pi = -1;
-              for (int j = 0; j < K; ++j) {
-                float bk = kNegInf;
-                int bi = 0x7fffffff;
-                for (int v = lane; v < V; v += 64) {
-                  const float k = rank_key(row[v] - lse);
-                  const bool after = key_beats(pk, pi, k, v);
-                  if (after & (v != a.blank) & key_beats(k, v, bk, bi)) {
-                    bk = k;
-                    bi = v;
-                  }
-                }
-                wave_kmax(bk, bi);
-                // top_k <= V - 1 non-blank elements: a winner exists in every round
-                bi = min(bi, V - 1);
-                if (lane == 0) {
-                  tk_idx[i][j] = bi;
-                  tk_lp[i][j] = row[bi] - lse;
-                }
-                pk = bk;
-                pi = bi;
-              }
-            }
+            if (expand)
+              topk_rounds_row(K, V, a.blank, lane, [&](int v) { return rank_key(row[v] - lse); },
+                              kmax, emit);
           }
         }
         __syncthreads();
@@ -461,52 +291,34 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
         if (lane == 0) n_a = na + __popcll(fresh);
         // a floor under the beam-th largest extension, so that few have to be ranked: the
         // beam-th largest among every hypothesis's two best (<= 64 values; nc > kRankAll means
-        // top_k >= 5).  An extension below it has `beam` above it.
+        // top_k >= 5)
         if (nc > kRankAll) {
           float v = kNegInf;
           if (lane < 2 * n) v = q.score[lane >> 1] + tk_lp[lane >> 1][lane & 1];
-          v = v > kNegInf ? v : kNegInf;
-          int above = 0;
-#pragma unroll 8
-          for (int o = 0; o < 64; ++o) {
-            const float ov = __shfl(v, o);
-            above += ((ov > v) | ((ov == v) & (o < lane))) ? 1 : 0;
-          }
-          if (above == Bm - 1) theta = v;
+          beam_floor(v, lane, Bm, &theta);
         }
       }
       __syncthreads();
       if (!expand) break;
-      // the extensions at or above the floor (-inf and NaN are dropped), as sortable keys:
-      // score, then the earlier candidate
-      const float floor_v = theta;
-      {   // candidate c = 32 i + j: one thread each, in the contract's order
-        const int c = opaque(tid), i = c >> 5, j = c & 31;
-        const float tc = (i < n && j < K) ? q.score[i] + tk_lp[i][j] : kNegInf;
-        if (tc > kNegInf && !(tc < floor_v)) keys[atomicAdd(&n_keys, 1)] = cand_key(tc, c);
-      }
-      __syncthreads();
-      // rank = number of candidates that beat this one; the first `beam` are the next round
-      const int nk = uniform(n_keys);
-      for (int k = opaque(tid); k < nk; k += kThreads) {
-        const uint64_t kc = keys[k];
-        const int c = (int)(0xffffffffu - (uint32_t)kc);
-        int rank = 0;
-#pragma unroll 4
-        for (int o = 0; o < nk; ++o) rank += keys[o] > kc ? 1 : 0;
-        if (rank >= Bm) continue;
-        atomicMax(&n_cnt[cur ^ 1], rank + 1);
-        const int i = c >> 5, j = c & 31;
-        const int tok = tk_idx[i][j], node = 1 + (f * MS + r) * Bm + rank;
-        nx.hash[rank] = hash_push(q.hash[i], tok);
-        nx.score[rank] = q.score[i] + tk_lp[i][j];
-        nx.node[rank] = node;
-        nx.len[rank] = q.len[i] + 1;
-        nx.last[rank] = tok;
-        s.trie[2 * (size_t)node] = q.node[i];
-        s.trie[2 * (size_t)node + 1] = tok;
-      }
-      __syncthreads();
+      // the extensions, candidate c = 32 i + j: one thread each, in the contract's order; the
+      // first `beam` are the next round
+      list_and_rank<4>(
+          tid, kThreads, kBeamMax * kTopkMax, theta, Bm, keys, &n_keys, &n_cnt[cur ^ 1],
+          [&](int c) {
+            const int i = c >> 5, j = c & 31;
+            return (i < n && j < K) ? q.score[i] + tk_lp[i][j] : kNegInf;
+          },
+          [&](int c, int rank) {
+            const int i = c >> 5, j = c & 31;
+            const int tok = tk_idx[i][j], node = 1 + (f * MS + r) * Bm + rank;
+            nx.hash[rank] = hash_push(q.hash[i], tok);
+            nx.score[rank] = q.score[i] + tk_lp[i][j];
+            nx.node[rank] = node;
+            nx.len[rank] = q.len[i] + 1;
+            nx.last[rank] = tok;
+            s.trie[2 * (size_t)node] = q.node[i];
+            s.trie[2 * (size_t)node + 1] = tok;
+          });
       cur ^= 1;
       n = uniform(n_cnt[cur]);
       if (n == 0) break;
@@ -521,37 +333,23 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
     __syncthreads();
     {
       Ents& nx = ents[cur ^ 1];
-      const int na = uniform(n_a);
-      for (int c = opaque(tid); c < na; c += kThreads) {
-        const float sc = A.score[c];
-        if (!(sc > kNegInf)) continue;
-        keys[atomicAdd(&n_keys, 1)] = cand_key(sc, c);
-      }
-      __syncthreads();
-      const int nk = uniform(n_keys);
-      for (int k = opaque(tid); k < nk; k += kThreads) {
-        const uint64_t kc = keys[k];
-        const int c = (int)(0xffffffffu - (uint32_t)kc);
-        int rank = 0;
-#pragma unroll 4
-        for (int o = 0; o < nk; ++o) rank += keys[o] > kc ? 1 : 0;
-        if (rank >= Bm) continue;
-        atomicMax(&n_cnt[cur ^ 1], rank + 1);
-        nx.hash[rank] = A.hash[c];
-        nx.score[rank] = A.score[c];
-        nx.node[rank] = A.node[c];
-        nx.len[rank] = A.len[c];
-        nx.last[rank] = A.last[c];
-      }
-      __syncthreads();
+      list_and_rank<4>(
+          tid, kThreads, uniform(n_a), kNegInf, Bm, keys, &n_keys, &n_cnt[cur ^ 1],
+          [&](int c) { return A.score[c]; },
+          [&](int c, int rank) {
+            nx.hash[rank] = A.hash[c];
+            nx.score[rank] = A.score[c];
+            nx.node[rank] = A.node[c];
+            nx.len[rank] = A.len[c];
+            nx.last[rank] = A.last[c];
+          });
       cur ^= 1;
       n = uniform(n_cnt[cur]);
     }
     ++f;
   }
   __syncthreads();
-  int ti = tid;
-  asm volatile("" : "+v"(ti));   // fresh addresses: the ones of the load above are not kept alive
+  const int ti = opaque(tid);   // fresh addresses: the ones of the load above are not kept alive
   if (ti < Bm) {   // entries past the alive ones leave in their reset form
     const Ents& q = ents[cur];
     const bool on = ti < n;
@@ -565,50 +363,6 @@ __global__ void __launch_bounds__(kThreads) rbeam_walk_kernel(WalkArgs a) {
     s.hdr[0] = f;
     s.hdr[1] = status;
     s.hdr[2] = n;
-  }
-}
-
-// ------------------------------------------------------------------ result -------------------
-struct ResultArgs {
-  const void* state;
-  size_t stream, hdr;
-  int B, beam, ms, nbest, cap, max_frames;
-  int32_t* tokens;
-  int32_t* frames;
-  int32_t* lens;
-  float* scores;
-  int32_t* status;
-};
-
-__global__ void __launch_bounds__(64) rbeam_result_kernel(ResultArgs a) {
-  const int b = blockIdx.x, i = threadIdx.x;
-  const View s = view((void*)a.state, a.stream, a.hdr, b, a.beam);
-  const bool ok = s.hdr[3] == (a.beam | (a.ms << 8));
-  if (i == 0 && a.status) a.status[b] = ok ? s.hdr[1] : 2;
-  if (i >= a.nbest) return;
-  const int64_t o = (int64_t)b * a.nbest + i;
-  const int n = ok ? min(max(s.hdr[2], 0), a.beam) : 0;
-  if (i >= n) {
-    a.lens[o] = -1;
-    a.scores[o] = kNegInf;
-    return;
-  }
-  const int L = s.len[i];
-  a.lens[o] = L;
-  a.scores[o] = s.score[i];
-  const int per = a.ms * a.beam;   // nodes of one live frame
-  const int64_t nodes = 1 + (int64_t)a.max_frames * per;
-  int node = s.node[i];
-  // backwards along the parent pointers, written forwards; a state that is not one (a node
-  // outside the trie) ends the walk
-  for (int pos = L - 1; pos >= 0 && node > 0 && node < nodes; --pos) {
-    const int parent = s.trie[2 * (size_t)node], tok = s.trie[2 * (size_t)node + 1];
-    if (pos < a.cap) {
-      a.tokens[o * a.cap + pos] = tok;
-      if (a.frames) a.frames[o * a.cap + pos] = (node - 1) / per;
-    }
-    if (parent >= node) break;   // parents precede their children
-    node = parent;
   }
 }
 
@@ -635,16 +389,8 @@ static bool launch_walk(const WalkArgs& a, bool fast, hipStream_t st) {
 using namespace sc;
 using namespace sc::rbeam;
 
-#define RBEAM_REQUIRE_SHAPE(fn, beam, ms)                                                        \
-  SC_REQUIRE((beam) >= 1 && (beam) <= kBeamMax, fn ": beam=%d outside [1, %d]", (beam), kBeamMax); \
-  SC_REQUIRE((ms) >= 1 && (ms) <= kSymMax, fn ": max_symbols=%d outside [1, %d]", (ms), kSymMax)
-
 extern "C" size_t sc_rnnt_beam_state_bytes(int B, int beam, int max_symbols, int max_frames) {
-  if (B < 0 || beam < 1 || beam > kBeamMax || max_symbols < 1 || max_symbols > kSymMax ||
-      max_frames < 0)
-    return 0;
-  if ((size_t)max_frames * (size_t)beam * (size_t)max_symbols >= (size_t)0x7ffffff0) return 0;
-  return (size_t)B * stream_bytes(beam, max_symbols, max_frames);
+  return beam_state_bytes(kNS, B, beam, max_symbols, max_frames);
 }
 
 extern "C" size_t sc_rnnt_beam_workspace_bytes(int B, int V) {
@@ -654,22 +400,8 @@ extern "C" size_t sc_rnnt_beam_workspace_bytes(int B, int V) {
 
 extern "C" int sc_rnnt_beam_reset(void* state, size_t state_bytes, int B, int beam, int max_symbols,
                                   int max_frames, const float* streams, void* stream) {
-  clear_error();
-  SC_REQUIRE(B >= 0, "sc_rnnt_beam_reset: bad shape B=%d", B);
-  RBEAM_REQUIRE_SHAPE("sc_rnnt_beam_reset", beam, max_symbols);
-  SC_REQUIRE(max_frames >= 0, "sc_rnnt_beam_reset: max_frames=%d is negative", max_frames);
-  if (B == 0) return 0;
-  SC_REQUIRE(state && ((uintptr_t)state & 7) == 0,
-             "sc_rnnt_beam_reset: state is a null pointer or not 8-byte aligned");
-  const size_t want = sc_rnnt_beam_state_bytes(B, beam, max_symbols, max_frames);
-  SC_REQUIRE(want != 0 && state_bytes == want,
-             "sc_rnnt_beam_reset: state_bytes=%zu is not sc_rnnt_beam_state_bytes(B=%d, beam=%d, "
-             "max_symbols=%d, max_frames=%d)=%zu", state_bytes, B, beam, max_symbols, max_frames,
-             want);
-  ResetArgs a{state, stream_bytes(beam, max_symbols, max_frames), hdr_bytes(beam), B, beam,
-              max_symbols, streams};
-  hipLaunchKernelGGL(rbeam_reset_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-  return launch_status("sc_rnnt_beam_reset");
+  return beam_reset<kNS>("sc_rnnt_beam_reset", state, state_bytes, B, beam, max_symbols, max_frames,
+                         streams, stream);
 }
 
 extern "C" int sc_rnnt_beam_frames(const void* enc_p, const void* pred_tab, const void* W, int dtype,
@@ -683,21 +415,19 @@ extern "C" int sc_rnnt_beam_frames(const void* enc_p, const void* pred_tab, cons
              "sc_rnnt_beam_frames: unsupported dtype %d", dtype);
   SC_REQUIRE(B >= 0 && T >= 0 && V > 0, "sc_rnnt_beam_frames: bad shape B=%d T=%d V=%d", B, T, V);
   SC_REQUIRE(J >= 1 && J <= kMaxJ, "sc_rnnt_beam_frames: J=%d outside [1, %d]", J, kMaxJ);
-  RBEAM_REQUIRE_SHAPE("sc_rnnt_beam_frames", beam, max_symbols);
+  if (beam_check_shape("sc_rnnt_beam_frames", kNS, beam, max_symbols)) return SC_EINVAL;
   SC_REQUIRE(top_k >= 1 && top_k <= kTopkMax, "sc_rnnt_beam_frames: top_k=%d outside [1, %d]",
              top_k, kTopkMax);
   SC_REQUIRE(blank >= 0 && blank < V, "sc_rnnt_beam_frames: blank=%d outside [0, V=%d)", blank, V);
   if (B == 0 || T == 0) return 0;
   SC_REQUIRE(enc_p && pred_tab && W && bias,
              "sc_rnnt_beam_frames: enc_p, pred_tab, W or bias is a null pointer");
-  SC_REQUIRE(state && ((uintptr_t)state & 7) == 0,
-             "sc_rnnt_beam_frames: state is a null pointer or not 8-byte aligned");
+  if (beam_check_state_ptr("sc_rnnt_beam_frames", state)) return SC_EINVAL;
   SC_REQUIRE(workspace && ((uintptr_t)workspace & 3) == 0,
              "sc_rnnt_beam_frames: workspace is a null pointer or not 4-byte aligned");
-  const Layout L = layout(state_bytes, B, beam, max_symbols);
-  SC_REQUIRE(L.max_frames >= 0,
-             "sc_rnnt_beam_frames: state_bytes=%zu is no sc_rnnt_beam_state_bytes(B=%d, beam=%d, "
-             "max_symbols=%d, .)", state_bytes, B, beam, max_symbols);
+  BeamLayout L;
+  if (beam_check_layout("sc_rnnt_beam_frames", kNS, state_bytes, B, beam, max_symbols, &L))
+    return SC_EINVAL;
   const size_t need = sc_rnnt_beam_workspace_bytes(B, V);
   SC_REQUIRE(workspace_bytes >= need, "sc_rnnt_beam_frames: workspace_bytes=%zu below the %zu of "
              "sc_rnnt_beam_workspace_bytes(B=%d, V=%d)", workspace_bytes, need, B, V);
@@ -722,23 +452,6 @@ extern "C" int sc_rnnt_beam_result(const void* state, size_t state_bytes, int B,
                                    int max_symbols, int nbest, int32_t* tokens, int32_t* frames,
                                    int cap, int32_t* lens, float* scores, int32_t* status,
                                    void* stream) {
-  clear_error();
-  SC_REQUIRE(B >= 0, "sc_rnnt_beam_result: bad shape B=%d", B);
-  RBEAM_REQUIRE_SHAPE("sc_rnnt_beam_result", beam, max_symbols);
-  SC_REQUIRE(nbest >= 1 && nbest <= beam, "sc_rnnt_beam_result: nbest=%d outside [1, beam=%d]",
-             nbest, beam);
-  SC_REQUIRE(cap >= 0, "sc_rnnt_beam_result: cap=%d is negative", cap);
-  if (B == 0) return 0;
-  SC_REQUIRE(state && ((uintptr_t)state & 7) == 0,
-             "sc_rnnt_beam_result: state is a null pointer or not 8-byte aligned");
-  SC_REQUIRE(lens && scores, "sc_rnnt_beam_result: lens or scores is a null pointer");
-  SC_REQUIRE(cap == 0 || tokens, "sc_rnnt_beam_result: tokens is a null pointer with cap=%d", cap);
-  const Layout L = layout(state_bytes, B, beam, max_symbols);
-  SC_REQUIRE(L.max_frames >= 0,
-             "sc_rnnt_beam_result: state_bytes=%zu is no sc_rnnt_beam_state_bytes(B=%d, beam=%d, "
-             "max_symbols=%d, .)", state_bytes, B, beam, max_symbols);
-  ResultArgs a{state, L.stream, L.hdr, B, beam, max_symbols, nbest, cap, (int)L.max_frames, tokens,
-               frames, lens, scores, status};
-  hipLaunchKernelGGL(rbeam_result_kernel, dim3(B), dim3(64), 0, (hipStream_t)stream, a);
-  return launch_status("sc_rnnt_beam_result");
+  return beam_result<kNS>("sc_rnnt_beam_result", state, state_bytes, B, beam, max_symbols, nbest,
+                          tokens, frames, cap, lens, scores, status, stream);
 }

@@ -14,13 +14,14 @@
 // One persistent workgroup of 1024 threads per stream; every branch is workgroup-uniform and every
 // loop is bounded by T, max_symbols, V or J.  One evaluation:
 //     wave 0: z -> LDS | barrier | every lane: its row(s) . z (z by broadcast 16-byte LDS reads),
-//     wave (value, index) reduction on DPP -> LDS | barrier | every wave reduces the 16 candidates
+//     wave (value, index) reduction on DPP (beam_common.h's wave_argmax in dec_beats' order) ->
+//     LDS | barrier | every wave reduces the 16 candidates
 //   rnnt_decode_kernel<DT, true>   J = 64, V <= 1024: lane v holds row v of W in 64 VGPRs + its bias
 //                                  for the whole stream (under the 128 VGPRs of 4 waves per SIMD)
 //   rnnt_decode_kernel<DT, false>  any V, J <= 256: rows v = tid, tid + 1024, ... read from memory
 //                                  at every evaluation (correct, not tuned)
 // enc_p[b,t+1] (and its mask) is loaded while frame t is resolved; pred_tab[u] only after an emission.
-#include "sc_common.h"
+#include "beam_common.h"
 
 namespace sc {
 
@@ -53,28 +54,6 @@ __device__ __forceinline__ bool dec_beats(float va, int ia, float vb, int ib) {
   const bool nan_win = na & (!nb | lower);
   const bool num_win = (va > vb) | ((va == vb) & lower);
   return (na | nb) ? nan_win : num_win;
-}
-
-// one DPP exchange inside a row of 16 lanes (every lane has a partner), keeping the winner
-template <int CTRL>
-__device__ __forceinline__ void amax_dpp(float& v, int& i) {
-  const float ov = __int_as_float(
-      __builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, 0xf, 0xf, false));
-  const int oi = __builtin_amdgcn_update_dpp(i, i, CTRL, 0xf, 0xf, false);
-  const bool take = dec_beats(ov, oi, v, i);
-  v = take ? ov : v;
-  i = take ? oi : i;
-}
-// after this every lane of a 16-lane row holds its row's winner
-__device__ __forceinline__ void row_argmax(float& v, int& i) {
-  amax_dpp<0xB1>(v, i);    // quad_perm [1,0,3,2]
-  amax_dpp<0x4E>(v, i);    // quad_perm [2,3,0,1]
-  amax_dpp<0x141>(v, i);   // row_half_mirror
-  amax_dpp<0x140>(v, i);   // row_mirror
-}
-
-__device__ __forceinline__ float dec_tanh(float x) {   // expf form, ~1e-7 absolute; NaN stays NaN
-  return 1.0f - 2.0f * rcp(exp2_(2.0f * kLog2e * x) + 1.0f);
 }
 
 template <int DT, bool FAST>
@@ -164,27 +143,16 @@ __global__ void __launch_bounds__(kDecThreads) rnnt_decode_kernel(RnntDecodeArgs
           }
         }
       }
-      // wave winner: rows of 16 on DPP, then the four row winners (lanes 0, 16, 32, 48)
-      row_argmax(bv, bi);
-      float wvv = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv), 0));
-      int wvi = __builtin_amdgcn_readlane(bi, 0);
-#pragma unroll
-      for (int r = 16; r < 64; r += 16) {
-        const float ov = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(bv), r));
-        const int oi = __builtin_amdgcn_readlane(bi, r);
-        const bool take = dec_beats(ov, oi, wvv, wvi);
-        wvv = take ? ov : wvv;
-        wvi = take ? oi : wvi;
-      }
+      wave_argmax<dec_beats>(bv, bi);
       if (lane == 0) {
-        cv[wv] = wvv;
-        ci[wv] = wvi;
+        cv[wv] = bv;
+        ci[wv] = bi;
       }
       lds_barrier();
       // every wave: the 16 wave winners, one per lane of each row
       float fv = cv[lane & (kDecWaves - 1)];
       int fi = ci[lane & (kDecWaves - 1)];
-      row_argmax(fv, fi);
+      row_argmax<dec_beats>(fv, fi);
       const int k = uniform(fi);
       if (k == a.blank) break;
       if (tid == 0 && count < a.cap) {

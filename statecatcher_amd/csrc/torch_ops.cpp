@@ -403,6 +403,25 @@ std::tuple<Tensor, Tensor> ctc_greedy_decode_meta(const Tensor& lp, const Tensor
   return {at::empty({lp.size(0), lp.size(1)}, io), at::empty({lp.size(0)}, io)};
 }
 
+// The optional lengths as a contiguous int64 tensor, and the optional mask's strides, of the
+// transducer and beam decoders
+optional<Tensor> decode_lengths(const optional<Tensor>& lengths_in, int64_t B, const char* me) {
+  optional<Tensor> lens;
+  if (lengths_in && lengths_in->defined()) {
+    lens = lengths_in->to(at::kLong).contiguous();
+    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
+  }
+  return lens;
+}
+
+std::pair<int64_t, int64_t> decode_mask_strides(const optional<Tensor>& mask, int64_t B, int64_t T,
+                                                const char* me) {
+  if (!(mask && mask->defined())) return {0, 0};
+  TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
+              mask->size(1) == T, me, "mask must be fp32 [B,T]");
+  return {mask->stride(0), mask->stride(1)};
+}
+
 // Greedy transducer decode of the stateless-predictor joiner (include/statecatcher.h,
 // sc_rnnt_greedy_decode).  frames is [B,cap] when return_frames, else an empty [B,0].
 std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_hip(
@@ -421,18 +440,8 @@ std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_hip(
   TORCH_CHECK(pred_tab.scalar_type() == enc.scalar_type() && W.scalar_type() == enc.scalar_type(),
               me, "enc_p, pred_tab and W must share one dtype");
   Tensor pc = pred_tab.contiguous(), wc = W.contiguous(), bc = f32c(bias);
-  optional<Tensor> lens;
-  if (lengths_in && lengths_in->defined()) {
-    lens = lengths_in->to(at::kLong).contiguous();
-    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
-  }
-  int64_t mb = 0, mt = 0;
-  if (mask && mask->defined()) {
-    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
-                mask->size(1) == T, me, "mask must be fp32 [B,T]");
-    mb = mask->stride(0);
-    mt = mask->stride(1);
-  }
+  optional<Tensor> lens = decode_lengths(lengths_in, B, me);
+  const auto [mb, mt] = decode_mask_strides(mask, B, T, me);
   if (prev && prev->defined())
     TORCH_CHECK(prev->scalar_type() == at::kInt && prev->numel() == B && prev->is_contiguous(), me,
                 "prev must be contiguous int32 [B]");
@@ -464,11 +473,59 @@ std::tuple<Tensor, Tensor, Tensor> rnnt_greedy_decode_meta(
   return {at::empty({B, cap}, io), at::empty({B}, io), at::empty({B, return_frames ? cap : 0}, io)};
 }
 
-// CTC prefix beam search (include/statecatcher.h, sc_ctc_beam_*).  The state is a uint8
-// [B, bytes per stream] tensor of ctc_beam_state_bytes(1, beam, max_frames) bytes per stream.
-void check_beam_state(const Tensor& state, const char* me) {
+// CTC prefix beam search and transducer beam search (include/statecatcher.h, sc_ctc_beam_*,
+// sc_rnnt_beam_*).  The state is a uint8 [B, bytes per stream] tensor of
+// ctc_beam_state_bytes(1, beam, max_frames) / rnnt_beam_state_bytes(1, beam, max_symbols,
+// max_frames) bytes per stream.  What the two sets of ops share:
+// the state's B after its check
+int64_t beam_state_streams(const Tensor& state, const char* me) {
   TORCH_CHECK(state.scalar_type() == at::kByte && state.dim() == 2 && state.is_contiguous(), me,
               "state must be a contiguous uint8 [B, bytes per stream] tensor");
+  return state.size(0);
+}
+
+const float* beam_reset_streams(const optional<Tensor>& streams, int64_t B, const char* me) {
+  if (streams && streams->defined())
+    TORCH_CHECK(streams->scalar_type() == at::kFloat && streams->numel() == B &&
+                streams->is_contiguous(), me, "streams must be contiguous fp32 [B]");
+  return (const float*)opt_ptr(streams);
+}
+
+// tokens, frames [B,nbest,cap] (-1 where nothing is written; frames only for the transducer),
+// lens, scores [B,nbest], status [B]; `like` gives device and B.  The meta functions get the
+// same shapes unfilled.
+struct BeamResult {
+  Tensor tokens, lens, scores, frames, status;
+};
+BeamResult beam_result_alloc(const Tensor& like, int64_t nbest, int64_t cap, bool frames,
+                             bool meta) {
+  const int64_t B = like.size(0);
+  auto io = like.options().dtype(at::kInt);
+  auto ids = [&] { return meta ? at::empty({B, nbest, cap}, io) : at::full({B, nbest, cap}, -1, io); };
+  BeamResult r;
+  r.tokens = ids();
+  if (frames) r.frames = ids();
+  r.lens = at::empty({B, nbest}, io);
+  r.scores = at::empty({B, nbest}, like.options().dtype(at::kFloat));
+  r.status = at::empty({B}, io);
+  return r;
+}
+
+BeamResult beam_result_checked(const Tensor& state, int64_t nbest, int64_t cap, bool frames,
+                               const char* me) {
+  beam_state_streams(state, me);
+  TORCH_CHECK(nbest >= 0 && nbest <= INT32_MAX && cap >= 0 && cap <= INT32_MAX, me,
+              "nbest or cap out of range");
+  return beam_result_alloc(state, nbest, cap, frames, false);
+}
+
+// offline: a fresh state of `per` bytes per stream of x, reset, the frames, the result
+template <class Reset, class Frames, class Result>
+auto beam_decode_offline(const Tensor& x, int64_t per, Reset reset, Frames frames, Result result) {
+  Tensor state = at::empty({x.size(0), per}, x.options().dtype(at::kByte));
+  reset(state);
+  frames(state);
+  return result(state);
 }
 
 int64_t ctc_beam_state_bytes(int64_t B, int64_t beam, int64_t max_frames) {
@@ -484,13 +541,10 @@ void ctc_beam_reset_hip(Tensor& state, int64_t beam, int64_t max_frames,
                         const optional<Tensor>& streams) {
   c10::DeviceGuard guard(state.device());
   const char* me = "statecatcher::ctc_beam_reset_: ";
-  check_beam_state(state, me);
-  const int64_t B = state.size(0);
-  if (streams && streams->defined())
-    TORCH_CHECK(streams->scalar_type() == at::kFloat && streams->numel() == B &&
-                streams->is_contiguous(), me, "streams must be contiguous fp32 [B]");
+  const int64_t B = beam_state_streams(state, me);
   sc_check(sc_ctc_beam_reset(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
-                             (int)max_frames, (const float*)opt_ptr(streams), stream_for(state)),
+                             (int)max_frames, beam_reset_streams(streams, B, me),
+                             stream_for(state)),
            "statecatcher::ctc_beam_reset_");
 }
 
@@ -503,22 +557,12 @@ void ctc_beam_frames_hip(const Tensor& x_in, Tensor& state, const optional<Tenso
   c10::DeviceGuard guard(x_in.device());
   const char* me = "statecatcher::ctc_beam_frames_: ";
   TORCH_CHECK(x_in.dim() == 3, me, "x must be [B,T,V]");
-  check_beam_state(state, me);
+  const int64_t SB = beam_state_streams(state, me);
   Tensor x = x_in.stride(2) == 1 || x_in.numel() == 0 ? x_in : x_in.contiguous();
   const int64_t B = x.size(0), T = x.size(1), V = x.size(2);
-  TORCH_CHECK(state.size(0) == B, me, "the state holds ", state.size(0), " streams, x has ", B);
-  optional<Tensor> lens;
-  if (lengths_in && lengths_in->defined()) {
-    lens = lengths_in->to(at::kLong).contiguous();
-    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
-  }
-  int64_t mb = 0, mt = 0;
-  if (mask && mask->defined()) {
-    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
-                mask->size(1) == T, me, "mask must be fp32 [B,T]");
-    mb = mask->stride(0);
-    mt = mask->stride(1);
-  }
+  TORCH_CHECK(SB == B, me, "the state holds ", SB, " streams, x has ", B);
+  optional<Tensor> lens = decode_lengths(lengths_in, B, me);
+  const auto [mb, mt] = decode_mask_strides(mask, B, T, me);
   TORCH_CHECK(B <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, me, "shape out of range");
   const size_t ws_bytes = sc_ctc_beam_workspace_bytes((int)B, (int)T, (int)top_k);
   Tensor ws = at::empty({(int64_t)ws_bytes}, x.options().dtype(at::kByte));
@@ -537,35 +581,24 @@ void ctc_beam_frames_meta(const Tensor& x, Tensor& state, const optional<Tensor>
               "statecatcher::ctc_beam_frames_: x [B,T,V], state [B, bytes per stream]");
 }
 
-// tokens [B,nbest,cap] (-1 where nothing is written), lens [B,nbest], scores [B,nbest], status [B]
 std::tuple<Tensor, Tensor, Tensor, Tensor> ctc_beam_result_hip(const Tensor& state, int64_t beam,
                                                                int64_t nbest, int64_t cap) {
   c10::DeviceGuard guard(state.device());
-  const char* me = "statecatcher::ctc_beam_result: ";
-  check_beam_state(state, me);
-  TORCH_CHECK(nbest >= 0 && nbest <= INT32_MAX && cap >= 0 && cap <= INT32_MAX, me,
-              "nbest or cap out of range");
-  const int64_t B = state.size(0);
-  auto io = state.options().dtype(at::kInt);
-  Tensor tokens = at::full({B, nbest, cap}, -1, io), lens = at::empty({B, nbest}, io);
-  Tensor scores = at::empty({B, nbest}, state.options().dtype(at::kFloat));
-  Tensor status = at::empty({B}, io);
-  sc_check(sc_ctc_beam_result(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam, (int)nbest,
-                              (int32_t*)tokens.data_ptr(), (int)cap, (int32_t*)lens.data_ptr(),
-                              (float*)scores.data_ptr(), (int32_t*)status.data_ptr(),
-                              stream_for(state)),
+  BeamResult r = beam_result_checked(state, nbest, cap, false, "statecatcher::ctc_beam_result: ");
+  sc_check(sc_ctc_beam_result(state.data_ptr(), (size_t)state.numel(), (int)state.size(0),
+                              (int)beam, (int)nbest, (int32_t*)r.tokens.data_ptr(), (int)cap,
+                              (int32_t*)r.lens.data_ptr(), (float*)r.scores.data_ptr(),
+                              (int32_t*)r.status.data_ptr(), stream_for(state)),
            "statecatcher::ctc_beam_result");
-  return {tokens, lens, scores, status};
+  return {r.tokens, r.lens, r.scores, r.status};
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor> ctc_beam_result_meta(const Tensor& state, int64_t beam,
                                                                 int64_t nbest, int64_t cap) {
   TORCH_CHECK(state.dim() == 2 && nbest >= 0 && cap >= 0,
               "statecatcher::ctc_beam_result: state [B, bytes per stream], nbest, cap >= 0");
-  const int64_t B = state.size(0);
-  auto io = state.options().dtype(at::kInt);
-  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
-          at::empty({B, nbest}, state.options().dtype(at::kFloat)), at::empty({B}, io)};
+  BeamResult r = beam_result_alloc(state, nbest, cap, false, true);
+  return {r.tokens, r.lens, r.scores, r.status};
 }
 
 // offline: a fresh state for max_frames (default T) live frames, the frames, the result
@@ -575,12 +608,12 @@ std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_hip(
     optional<int64_t> cap_in) {
   c10::DeviceGuard guard(x.device());
   TORCH_CHECK(x.dim() == 3, "statecatcher::ctc_beam_decode: x must be [B,T,V]");
-  const int64_t B = x.size(0), max_frames = max_frames_in ? *max_frames_in : x.size(1);
-  const int64_t per = ctc_beam_state_bytes(1, beam, max_frames);
-  Tensor state = at::empty({B, per}, x.options().dtype(at::kByte));
-  ctc_beam_reset_hip(state, beam, max_frames, c10::nullopt);
-  ctc_beam_frames_hip(x, state, lengths, mask, blank, beam, top_k, is_logits);
-  auto r = ctc_beam_result_hip(state, beam, nbest, cap_in ? *cap_in : max_frames);
+  const int64_t max_frames = max_frames_in ? *max_frames_in : x.size(1);
+  auto r = beam_decode_offline(
+      x, ctc_beam_state_bytes(1, beam, max_frames),
+      [&](Tensor& st) { ctc_beam_reset_hip(st, beam, max_frames, c10::nullopt); },
+      [&](Tensor& st) { ctc_beam_frames_hip(x, st, lengths, mask, blank, beam, top_k, is_logits); },
+      [&](Tensor& st) { return ctc_beam_result_hip(st, beam, nbest, cap_in ? *cap_in : max_frames); });
   return {std::get<0>(r), std::get<1>(r), std::get<2>(r)};
 }
 
@@ -589,16 +622,11 @@ std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_meta(
     int64_t beam, int64_t top_k, int64_t nbest, bool is_logits, optional<int64_t> max_frames_in,
     optional<int64_t> cap_in) {
   TORCH_CHECK(x.dim() == 3 && nbest >= 0, "statecatcher::ctc_beam_decode: x must be [B,T,V]");
-  const int64_t B = x.size(0), max_frames = max_frames_in ? *max_frames_in : x.size(1);
-  const int64_t cap = cap_in ? *cap_in : max_frames;
-  auto io = x.options().dtype(at::kInt);
-  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
-          at::empty({B, nbest}, x.options().dtype(at::kFloat))};
+  const int64_t max_frames = max_frames_in ? *max_frames_in : x.size(1);
+  BeamResult r = beam_result_alloc(x, nbest, cap_in ? *cap_in : max_frames, false, true);
+  return {r.tokens, r.lens, r.scores};
 }
 
-// Transducer beam search (include/statecatcher.h, sc_rnnt_beam_*).  The state is a uint8
-// [B, bytes per stream] tensor of rnnt_beam_state_bytes(1, beam, max_symbols, max_frames) bytes
-// per stream.
 int64_t rnnt_beam_state_bytes(int64_t B, int64_t beam, int64_t max_symbols, int64_t max_frames) {
   TORCH_CHECK(B >= 0 && B <= INT32_MAX && max_frames >= 0 && max_frames <= INT32_MAX,
               "statecatcher::rnnt_beam_state_bytes: B or max_frames out of range");
@@ -613,14 +641,10 @@ void rnnt_beam_reset_hip(Tensor& state, int64_t beam, int64_t max_symbols, int64
                          const optional<Tensor>& streams) {
   c10::DeviceGuard guard(state.device());
   const char* me = "statecatcher::rnnt_beam_reset_: ";
-  check_beam_state(state, me);
-  const int64_t B = state.size(0);
-  if (streams && streams->defined())
-    TORCH_CHECK(streams->scalar_type() == at::kFloat && streams->numel() == B &&
-                streams->is_contiguous(), me, "streams must be contiguous fp32 [B]");
+  const int64_t B = beam_state_streams(state, me);
   sc_check(sc_rnnt_beam_reset(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
-                              (int)max_symbols, (int)max_frames, (const float*)opt_ptr(streams),
-                              stream_for(state)),
+                              (int)max_symbols, (int)max_frames,
+                              beam_reset_streams(streams, B, me), stream_for(state)),
            "statecatcher::rnnt_beam_reset_");
 }
 
@@ -635,27 +659,17 @@ void rnnt_beam_frames_hip(const Tensor& enc_in, const Tensor& pred_tab, const Te
   const char* me = "statecatcher::rnnt_beam_frames_: ";
   TORCH_CHECK(enc_in.dim() == 3 && pred_tab.dim() == 2 && W.dim() == 2 && bias.dim() == 1, me,
               "enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]");
-  check_beam_state(state, me);
+  const int64_t SB = beam_state_streams(state, me);
   Tensor enc = enc_in.stride(2) == 1 || enc_in.numel() == 0 ? enc_in : enc_in.contiguous();
   const int64_t B = enc.size(0), T = enc.size(1), J = enc.size(2), V = W.size(0);
   TORCH_CHECK(W.size(1) == J && pred_tab.size(0) == V && pred_tab.size(1) == J && bias.numel() == V,
               me, "pred_tab / W must be [V,J] and bias [V]");
   TORCH_CHECK(pred_tab.scalar_type() == enc.scalar_type() && W.scalar_type() == enc.scalar_type(),
               me, "enc_p, pred_tab and W must share one dtype");
-  TORCH_CHECK(state.size(0) == B, me, "the state holds ", state.size(0), " streams, enc_p has ", B);
+  TORCH_CHECK(SB == B, me, "the state holds ", SB, " streams, enc_p has ", B);
   Tensor pc = pred_tab.contiguous(), wc = W.contiguous(), bc = f32c(bias);
-  optional<Tensor> lens;
-  if (lengths_in && lengths_in->defined()) {
-    lens = lengths_in->to(at::kLong).contiguous();
-    TORCH_CHECK(lens->numel() == B, me, "lengths must have B entries");
-  }
-  int64_t mb = 0, mt = 0;
-  if (mask && mask->defined()) {
-    TORCH_CHECK(mask->scalar_type() == at::kFloat && mask->dim() == 2 && mask->size(0) == B &&
-                mask->size(1) == T, me, "mask must be fp32 [B,T]");
-    mb = mask->stride(0);
-    mt = mask->stride(1);
-  }
+  optional<Tensor> lens = decode_lengths(lengths_in, B, me);
+  const auto [mb, mt] = decode_mask_strides(mask, B, T, me);
   TORCH_CHECK(B <= INT32_MAX && T <= INT32_MAX && V <= INT32_MAX, me, "shape out of range");
   const size_t ws_bytes = sc_rnnt_beam_workspace_bytes((int)B, (int)V);
   Tensor ws = at::empty({(int64_t)(ws_bytes ? ws_bytes : 4)}, enc.options().dtype(at::kByte));
@@ -678,38 +692,25 @@ void rnnt_beam_frames_meta(const Tensor& enc, const Tensor& pred_tab, const Tens
               "statecatcher::rnnt_beam_frames_: enc_p [B,T,J], W [V,J], state [B, bytes per stream]");
 }
 
-// tokens, frames [B,nbest,cap] (-1 where nothing is written), lens, scores [B,nbest], status [B]
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rnnt_beam_result_hip(
     const Tensor& state, int64_t beam, int64_t max_symbols, int64_t nbest, int64_t cap) {
   c10::DeviceGuard guard(state.device());
-  const char* me = "statecatcher::rnnt_beam_result: ";
-  check_beam_state(state, me);
-  TORCH_CHECK(nbest >= 0 && nbest <= INT32_MAX && cap >= 0 && cap <= INT32_MAX, me,
-              "nbest or cap out of range");
-  const int64_t B = state.size(0);
-  auto io = state.options().dtype(at::kInt);
-  Tensor tokens = at::full({B, nbest, cap}, -1, io), frames = at::full({B, nbest, cap}, -1, io);
-  Tensor lens = at::empty({B, nbest}, io);
-  Tensor scores = at::empty({B, nbest}, state.options().dtype(at::kFloat));
-  Tensor status = at::empty({B}, io);
-  sc_check(sc_rnnt_beam_result(state.data_ptr(), (size_t)state.numel(), (int)B, (int)beam,
-                               (int)max_symbols, (int)nbest, (int32_t*)tokens.data_ptr(),
-                               (int32_t*)frames.data_ptr(), (int)cap, (int32_t*)lens.data_ptr(),
-                               (float*)scores.data_ptr(), (int32_t*)status.data_ptr(),
-                               stream_for(state)),
+  BeamResult r = beam_result_checked(state, nbest, cap, true, "statecatcher::rnnt_beam_result: ");
+  sc_check(sc_rnnt_beam_result(state.data_ptr(), (size_t)state.numel(), (int)state.size(0),
+                               (int)beam, (int)max_symbols, (int)nbest,
+                               (int32_t*)r.tokens.data_ptr(), (int32_t*)r.frames.data_ptr(),
+                               (int)cap, (int32_t*)r.lens.data_ptr(), (float*)r.scores.data_ptr(),
+                               (int32_t*)r.status.data_ptr(), stream_for(state)),
            "statecatcher::rnnt_beam_result");
-  return {tokens, lens, scores, frames, status};
+  return {r.tokens, r.lens, r.scores, r.frames, r.status};
 }
 
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> rnnt_beam_result_meta(
     const Tensor& state, int64_t beam, int64_t max_symbols, int64_t nbest, int64_t cap) {
   TORCH_CHECK(state.dim() == 2 && nbest >= 0 && cap >= 0,
               "statecatcher::rnnt_beam_result: state [B, bytes per stream], nbest, cap >= 0");
-  const int64_t B = state.size(0);
-  auto io = state.options().dtype(at::kInt);
-  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
-          at::empty({B, nbest}, state.options().dtype(at::kFloat)), at::empty({B, nbest, cap}, io),
-          at::empty({B}, io)};
+  BeamResult r = beam_result_alloc(state, nbest, cap, true, true);
+  return {r.tokens, r.lens, r.scores, r.frames, r.status};
 }
 
 // offline: a fresh state for max_frames (default T) live frames, the frames, the result
@@ -720,14 +721,16 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> rnnt_beam_decode_hip(
     optional<int64_t> cap_in) {
   c10::DeviceGuard guard(enc.device());
   TORCH_CHECK(enc.dim() == 3, "statecatcher::rnnt_beam_decode: enc_p must be [B,T,J]");
-  const int64_t B = enc.size(0), max_frames = max_frames_in ? *max_frames_in : enc.size(1);
-  const int64_t per = rnnt_beam_state_bytes(1, beam, max_symbols, max_frames);
-  Tensor state = at::empty({B, per}, enc.options().dtype(at::kByte));
-  rnnt_beam_reset_hip(state, beam, max_symbols, max_frames, c10::nullopt);
-  rnnt_beam_frames_hip(enc, pred_tab, W, bias, state, lengths, mask, blank, beam, top_k,
-                       max_symbols);
-  auto r = rnnt_beam_result_hip(state, beam, max_symbols, nbest,
-                                cap_in ? *cap_in : max_frames * max_symbols);
+  const int64_t max_frames = max_frames_in ? *max_frames_in : enc.size(1);
+  const int64_t cap = cap_in ? *cap_in : max_frames * max_symbols;
+  auto r = beam_decode_offline(
+      enc, rnnt_beam_state_bytes(1, beam, max_symbols, max_frames),
+      [&](Tensor& st) { rnnt_beam_reset_hip(st, beam, max_symbols, max_frames, c10::nullopt); },
+      [&](Tensor& st) {
+        rnnt_beam_frames_hip(enc, pred_tab, W, bias, st, lengths, mask, blank, beam, top_k,
+                             max_symbols);
+      },
+      [&](Tensor& st) { return rnnt_beam_result_hip(st, beam, max_symbols, nbest, cap); });
   return {std::get<0>(r), std::get<1>(r), std::get<2>(r), std::get<3>(r)};
 }
 
@@ -737,11 +740,10 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> rnnt_beam_decode_meta(
     int64_t top_k, int64_t max_symbols, int64_t nbest, optional<int64_t> max_frames_in,
     optional<int64_t> cap_in) {
   TORCH_CHECK(enc.dim() == 3 && nbest >= 0, "statecatcher::rnnt_beam_decode: enc_p must be [B,T,J]");
-  const int64_t B = enc.size(0), max_frames = max_frames_in ? *max_frames_in : enc.size(1);
-  const int64_t cap = cap_in ? *cap_in : max_frames * max_symbols;
-  auto io = enc.options().dtype(at::kInt);
-  return {at::empty({B, nbest, cap}, io), at::empty({B, nbest}, io),
-          at::empty({B, nbest}, enc.options().dtype(at::kFloat)), at::empty({B, nbest, cap}, io)};
+  const int64_t max_frames = max_frames_in ? *max_frames_in : enc.size(1);
+  BeamResult r = beam_result_alloc(enc, nbest, cap_in ? *cap_in : max_frames * max_symbols, true,
+                                   true);
+  return {r.tokens, r.lens, r.scores, r.frames};
 }
 
 // ------------------------------------------------------------------------------ mLSTM --------

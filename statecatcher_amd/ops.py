@@ -1303,6 +1303,35 @@ def ctc_greedy_frames(logits, prev, emit, mask=None, blank=0):
     check(rc, "sc_ctc_greedy_frames")
 
 
+def _joiner_args(me, enc_p, pred_tab, W, bias, lengths, mask, prev=None):
+    """The checks rnnt_greedy_decode and rnnt_beam_decode (``me``) share on a joiner's tensors
+    -> (B, T, V, J, lengths as an int64 device tensor or None)."""
+    require_device(enc_p, pred_tab, W, bias, prev, mask)
+    if enc_p.dim() != 3 or pred_tab.dim() != 2 or W.dim() != 2 or bias.dim() != 1:
+        raise ValueError(f"{me}: enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]")
+    B, T, J = enc_p.shape
+    V = W.shape[0]
+    if tuple(W.shape) != (V, J) or tuple(pred_tab.shape) != (V, J) or bias.numel() != V:
+        raise ValueError(f"{me}: pred_tab / W must be [V,J]=[{V},{J}] and bias [V], "
+                         f"got {tuple(pred_tab.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}")
+    if pred_tab.dtype != enc_p.dtype or W.dtype != enc_p.dtype:
+        raise ValueError(f"{me}: enc_p, pred_tab and W must share one dtype")
+    if bias.dtype != torch.float32 or not bias.is_contiguous():
+        raise ValueError(f"{me}: bias must be contiguous fp32 [V]")
+    if (T > 0 and B > 0 and enc_p.stride(2) != 1) or not pred_tab.is_contiguous() \
+            or not W.is_contiguous():
+        raise ValueError(f"{me}: enc_p needs unit inner stride, pred_tab / W contiguous")
+    if prev is not None and (prev.dtype != torch.int32 or prev.numel() != B
+                             or not prev.is_contiguous()):
+        raise ValueError(f"{me}: prev must be contiguous int32 [B]")
+    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
+        raise ValueError(f"{me}: mask must be fp32 [B, T]")
+    lens = None if lengths is None else _as_len_tensor(lengths, enc_p.device)
+    if lens is not None and lens.numel() != B:
+        raise ValueError(f"{me}: lengths must have B entries")
+    return B, T, V, J, lens
+
+
 def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, max_symbols=4,
                        prev=None, cap=None, return_frames=False, out=None):
     """Greedy transducer decode of a stateless-predictor joiner in one launch
@@ -1318,29 +1347,8 @@ def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=
     cap defaults to T * max_symbols, which cannot overflow.  out = (tokens, counts, frames or
     None): write into these instead of allocating (no allocation then: safe inside a hipGraph
     capture).  No host sync (a ``lengths`` list is copied to the device asynchronously)."""
-    require_device(enc_p, pred_tab, W, bias, prev, mask)
-    if enc_p.dim() != 3 or pred_tab.dim() != 2 or W.dim() != 2 or bias.dim() != 1:
-        raise ValueError("rnnt_greedy_decode: enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]")
-    B, T, J = enc_p.shape
-    V = W.shape[0]
-    if tuple(W.shape) != (V, J) or tuple(pred_tab.shape) != (V, J) or bias.numel() != V:
-        raise ValueError(f"rnnt_greedy_decode: pred_tab / W must be [V,J]=[{V},{J}] and bias [V], "
-                         f"got {tuple(pred_tab.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}")
-    if pred_tab.dtype != enc_p.dtype or W.dtype != enc_p.dtype:
-        raise ValueError("rnnt_greedy_decode: enc_p, pred_tab and W must share one dtype")
-    if bias.dtype != torch.float32 or not bias.is_contiguous():
-        raise ValueError("rnnt_greedy_decode: bias must be contiguous fp32 [V]")
-    if (T > 0 and B > 0 and enc_p.stride(2) != 1) or not pred_tab.is_contiguous() \
-            or not W.is_contiguous():
-        raise ValueError("rnnt_greedy_decode: enc_p needs unit inner stride, pred_tab / W contiguous")
-    if prev is not None and (prev.dtype != torch.int32 or prev.numel() != B
-                             or not prev.is_contiguous()):
-        raise ValueError("rnnt_greedy_decode: prev must be contiguous int32 [B]")
-    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
-        raise ValueError("rnnt_greedy_decode: mask must be fp32 [B, T]")
-    lens = None if lengths is None else _as_len_tensor(lengths, enc_p.device)
-    if lens is not None and lens.numel() != B:
-        raise ValueError("rnnt_greedy_decode: lengths must have B entries")
+    B, T, V, J, lens = _joiner_args("rnnt_greedy_decode", enc_p, pred_tab, W, bias, lengths, mask,
+                                    prev)
     if out is not None:
         tokens, counts, frames = out
         cap = tokens.shape[1]
@@ -1370,25 +1378,23 @@ def rnnt_greedy_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=
     return (tokens, counts, frames) if return_frames else (tokens, counts)
 
 
-class CtcBeamState:
-    """The state of B CTC prefix beam search streams (include/statecatcher.h, sc_ctc_beam_*):
-    ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its
-    status word and its token trie for ``max_frames`` live frames.  Made reset; ``reset()`` starts
-    every stream afresh, ``reset(streams)`` the listed stream indices (or, given a fp32 [B]
-    tensor, the streams whose entry is non-zero; no allocation then)."""
+class _BeamState:
+    """What CtcBeamState and RnntBeamState share: ``buf`` uint8 [B, bytes per stream], made
+    reset, and the decoder's workspace.  A subclass sets B, beam, max_frames (and max_symbols),
+    names itself (``_name``) and binds the library's size and reset calls (``_size_args`` are the
+    arguments of both after B, ``_ws_min`` the least workspace)."""
+    _name, _ws_min = None, 0
 
-    def __init__(self, B, beam, max_frames, device):
+    def _make(self, B, device, limits):
         lib = _lib.load()
-        B, beam, max_frames = int(B), int(beam), int(max_frames)
-        nbytes = lib.sc_ctc_beam_state_bytes(max(B, 1), beam, max_frames)
+        nbytes = getattr(lib, f"sc_{self._name}_state_bytes")(max(B, 1), *self._size_args())
         if B < 0 or nbytes == 0:
-            raise ValueError(f"ctc_beam_state: B={B}, beam={beam} (1..32), max_frames={max_frames} "
-                             "(>= 0, max_frames * beam < 2^31) do not describe a state")
+            raise ValueError(f"{self._name}_state: B={B}, {limits} do not describe a state")
         device = torch.device(device)
         if device.type != "cuda":
             raise RuntimeError("statecatcher ops run only on a ROCm GPU (HIP); got device "
                                f"{device}. There is no CPU fallback.")
-        self.B, self.beam, self.max_frames = B, beam, max_frames
+        self.B = B
         self.buf = torch.zeros(B, nbytes // max(B, 1), dtype=torch.uint8, device=device)
         self._ws = None
         self.reset()
@@ -1404,24 +1410,77 @@ class CtcBeamState:
             streams = m.to(self.buf.device, non_blocking=True)
         if streams is not None and (streams.dtype != torch.float32 or streams.numel() != self.B
                                     or not streams.is_contiguous()):
-            raise ValueError("ctc_beam_state.reset: streams must be contiguous fp32 [B]")
+            raise ValueError(f"{self._name}_state.reset: streams must be contiguous fp32 [B]")
         require_device(streams)
-        rc = _lib.load().sc_ctc_beam_reset(ptr(self.buf), self.nbytes, self.B, self.beam,
-                                           self.max_frames, ptr(streams), stream_of(self.buf))
-        check(rc, "sc_ctc_beam_reset")
+        fn = f"sc_{self._name}_reset"
+        rc = getattr(_lib.load(), fn)(ptr(self.buf), self.nbytes, self.B, *self._size_args(),
+                                      ptr(streams), stream_of(self.buf))
+        check(rc, fn)
 
     def workspace(self, nbytes):
-        """The pre-pass workspace, grown when a call needs more (kept between calls, so a chunk
+        """The decoder's workspace, grown when a call needs more (kept between calls, so a chunk
         call of a fixed shape allocates once)."""
         if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=self.buf.device)
+            self._ws = torch.empty(max(nbytes, self._ws_min), dtype=torch.uint8,
+                                   device=self.buf.device)
         return self._ws
+
+
+class CtcBeamState(_BeamState):
+    """The state of B CTC prefix beam search streams (include/statecatcher.h, sc_ctc_beam_*):
+    ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its
+    status word and its token trie for ``max_frames`` live frames.  Made reset; ``reset()`` starts
+    every stream afresh, ``reset(streams)`` the listed stream indices (or, given a fp32 [B]
+    tensor, the streams whose entry is non-zero; no allocation then)."""
+    _name = "ctc_beam"
+
+    def __init__(self, B, beam, max_frames, device):
+        self.beam, self.max_frames = int(beam), int(max_frames)
+        self._make(int(B), device, f"beam={self.beam} (1..32), max_frames={self.max_frames} "
+                   "(>= 0, max_frames * beam < 2^31)")
+
+    def _size_args(self):
+        return self.beam, self.max_frames
 
 
 def ctc_beam_state(B, beam, max_frames, device):
     """A reset CtcBeamState for chunked ctc_beam_decode: B streams, beam width ``beam``, room for
     ``max_frames`` live frames per stream."""
     return CtcBeamState(B, beam, max_frames, device)
+
+
+def _beam_result_buffers(me, state, nbest, cap, out, frames, return_status):
+    """The buffers of ctc_beam_result / rnnt_beam_result (``me``): ``out`` validated, or fresh
+    ones with tokens (and frames) filled with -1 -> (tokens, lens, scores, frames, status, cap).
+    ``frames`` is None for a decoder without frames (out has three entries then), else whether
+    fresh buffers include them (out may have a fourth entry)."""
+    B, dev, has_frames = state.B, state.buf.device, frames is not None
+    if out is not None:
+        tokens, lens, scores = out[:3] if has_frames else out
+        frames = out[3] if has_frames and len(out) > 3 else None
+        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 3 \
+            and tuple(tokens.shape[:2]) == (B, nbest) and lens.dtype == torch.int32 \
+            and lens.is_contiguous() and tuple(lens.shape) == (B, nbest) \
+            and scores.dtype == torch.float32 and scores.is_contiguous() \
+            and tuple(scores.shape) == (B, nbest) \
+            and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous()
+                                    and frames.shape == tokens.shape))
+        if not ok:
+            raise ValueError(f"{me}: out = (tokens int32 [B,nbest,cap], lens int32 [B,nbest], "
+                             f"scores fp32 [B,nbest]{'[, frames as tokens]' if has_frames else ''}"
+                             "), contiguous")
+        require_device(tokens, lens, scores, frames)
+        cap = tokens.shape[2]
+    else:
+        cap = int(cap)
+        if cap < 0 or nbest < 0:
+            raise ValueError(f"{me}: cap={cap} or nbest={nbest} is negative")
+        tokens = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
+        lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
+        frames = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev) if frames else None
+    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    return tokens, lens, scores, frames, status, cap
 
 
 def ctc_beam_result(state, nbest=1, cap=None, out=None, return_status=False):
@@ -1433,27 +1492,9 @@ def ctc_beam_result(state, nbest=1, cap=None, out=None, return_status=False):
     write into these instead of allocating (tokens is not filled then).  status bit 0: the stream
     met more than max_frames live frames and ignored the rest."""
     B, nbest = state.B, int(nbest)
-    dev = state.buf.device
-    if out is not None:
-        tokens, lens, scores = out
-        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 3 \
-            and tuple(tokens.shape[:2]) == (B, nbest) and lens.dtype == torch.int32 \
-            and lens.is_contiguous() and tuple(lens.shape) == (B, nbest) \
-            and scores.dtype == torch.float32 and scores.is_contiguous() \
-            and tuple(scores.shape) == (B, nbest)
-        if not ok:
-            raise ValueError("ctc_beam_result: out = (tokens int32 [B,nbest,cap], lens int32 "
-                             "[B,nbest], scores fp32 [B,nbest]), contiguous")
-        require_device(tokens, lens, scores)
-        cap = tokens.shape[2]
-    else:
-        cap = state.max_frames if cap is None else int(cap)
-        if cap < 0 or nbest < 0:
-            raise ValueError(f"ctc_beam_result: cap={cap} or nbest={nbest} is negative")
-        tokens = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
-        lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    tokens, lens, scores, _, status, cap = _beam_result_buffers(
+        "ctc_beam_result", state, nbest, state.max_frames if cap is None else cap, out, None,
+        return_status)
     rc = _lib.load().sc_ctc_beam_result(ptr(state.buf), state.nbytes, B, state.beam, nbest,
                                         ptr(tokens), cap, ptr(lens), ptr(scores), ptr(status),
                                         stream_of(state.buf))
@@ -1507,55 +1548,23 @@ def ctc_beam_decode(log_probs_or_logits, lengths=None, mask=None, blank=0, beam=
     return ctc_beam_result(state, nbest, cap, out)
 
 
-class RnntBeamState:
+class RnntBeamState(_BeamState):
     """The state of B transducer beam search streams (include/statecatcher.h, sc_rnnt_beam_*):
     ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its
     status word and its token trie for ``max_frames`` live frames of at most ``max_symbols``
     tokens.  Made reset; ``reset()`` starts every stream afresh, ``reset(streams)`` the listed
     stream indices (or, given a fp32 [B] tensor, the streams whose entry is non-zero; no
     allocation then)."""
+    _name, _ws_min = "rnnt_beam", 4
 
     def __init__(self, B, beam, max_symbols, max_frames, device):
-        lib = _lib.load()
-        B, beam, max_symbols, max_frames = int(B), int(beam), int(max_symbols), int(max_frames)
-        nbytes = lib.sc_rnnt_beam_state_bytes(max(B, 1), beam, max_symbols, max_frames)
-        if B < 0 or nbytes == 0:
-            raise ValueError(f"rnnt_beam_state: B={B}, beam={beam} (1..32), max_symbols="
-                             f"{max_symbols} (1..8), max_frames={max_frames} (>= 0, max_frames * "
-                             "max_symbols * beam < 2^31) do not describe a state")
-        device = torch.device(device)
-        if device.type != "cuda":
-            raise RuntimeError("statecatcher ops run only on a ROCm GPU (HIP); got device "
-                               f"{device}. There is no CPU fallback.")
-        self.B, self.beam, self.max_symbols, self.max_frames = B, beam, max_symbols, max_frames
-        self.buf = torch.zeros(B, nbytes // max(B, 1), dtype=torch.uint8, device=device)
-        self._ws = None
-        self.reset()
+        self.beam, self.max_symbols, self.max_frames = int(beam), int(max_symbols), int(max_frames)
+        self._make(int(B), device, f"beam={self.beam} (1..32), max_symbols={self.max_symbols} "
+                   f"(1..8), max_frames={self.max_frames} (>= 0, max_frames * max_symbols * beam "
+                   "< 2^31)")
 
-    @property
-    def nbytes(self):
-        return self.buf.numel()
-
-    def reset(self, streams=None):
-        if streams is not None and not isinstance(streams, torch.Tensor):
-            m = torch.zeros(self.B, dtype=torch.float32)
-            m[list(streams)] = 1.0
-            streams = m.to(self.buf.device, non_blocking=True)
-        if streams is not None and (streams.dtype != torch.float32 or streams.numel() != self.B
-                                    or not streams.is_contiguous()):
-            raise ValueError("rnnt_beam_state.reset: streams must be contiguous fp32 [B]")
-        require_device(streams)
-        rc = _lib.load().sc_rnnt_beam_reset(ptr(self.buf), self.nbytes, self.B, self.beam,
-                                            self.max_symbols, self.max_frames, ptr(streams),
-                                            stream_of(self.buf))
-        check(rc, "sc_rnnt_beam_reset")
-
-    def workspace(self, nbytes):
-        """The walk's workspace, grown when a call needs more (kept between calls, so a chunk
-        call of a fixed shape allocates once)."""
-        if self._ws is None or self._ws.numel() < nbytes:
-            self._ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.buf.device)
-        return self._ws
+    def _size_args(self):
+        return self.beam, self.max_symbols, self.max_frames
 
 
 def rnnt_beam_state(B, beam, max_symbols, max_frames, device):
@@ -1575,34 +1584,11 @@ def rnnt_beam_result(state, nbest=1, cap=None, out=None, return_frames=False, re
     (they are not filled then).  status bit 0: the stream met more than max_frames live frames
     and ignored the rest."""
     B, nbest = state.B, int(nbest)
-    dev = state.buf.device
-    frames = None
-    if out is not None:
-        tokens, lens, scores = out[:3]
-        frames = out[3] if len(out) > 3 else None
-        ok = tokens.dtype == torch.int32 and tokens.is_contiguous() and tokens.dim() == 3 \
-            and tuple(tokens.shape[:2]) == (B, nbest) and lens.dtype == torch.int32 \
-            and lens.is_contiguous() and tuple(lens.shape) == (B, nbest) \
-            and scores.dtype == torch.float32 and scores.is_contiguous() \
-            and tuple(scores.shape) == (B, nbest) \
-            and (frames is None or (frames.dtype == torch.int32 and frames.is_contiguous()
-                                    and frames.shape == tokens.shape))
-        if not ok:
-            raise ValueError("rnnt_beam_result: out = (tokens int32 [B,nbest,cap], lens int32 "
-                             "[B,nbest], scores fp32 [B,nbest][, frames as tokens]), contiguous")
-        require_device(tokens, lens, scores, frames)
-        cap = tokens.shape[2]
-        return_frames = frames is not None
-    else:
-        cap = state.max_frames * state.max_symbols if cap is None else int(cap)
-        if cap < 0 or nbest < 0:
-            raise ValueError(f"rnnt_beam_result: cap={cap} or nbest={nbest} is negative")
-        tokens = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
-        lens = torch.empty(B, nbest, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, nbest, dtype=torch.float32, device=dev)
-        if return_frames:
-            frames = torch.full((B, nbest, cap), -1, dtype=torch.int32, device=dev)
-    status = torch.empty(B, dtype=torch.int32, device=dev) if return_status else None
+    tokens, lens, scores, frames, status, cap = _beam_result_buffers(
+        "rnnt_beam_result", state, nbest,
+        state.max_frames * state.max_symbols if cap is None else cap, out, bool(return_frames),
+        return_status)
+    return_frames = frames is not None
     rc = _lib.load().sc_rnnt_beam_result(ptr(state.buf), state.nbytes, B, state.beam,
                                          state.max_symbols, nbest, ptr(tokens), ptr(frames), cap,
                                          ptr(lens), ptr(scores), ptr(status), stream_of(state.buf))
@@ -1635,26 +1621,7 @@ def rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0,
     and out= the call allocates nothing once the state's workspace has its size (safe inside a
     hipGraph capture).  No host sync (a ``lengths`` list is copied to the device
     asynchronously)."""
-    require_device(enc_p, pred_tab, W, bias, mask)
-    if enc_p.dim() != 3 or pred_tab.dim() != 2 or W.dim() != 2 or bias.dim() != 1:
-        raise ValueError("rnnt_beam_decode: enc_p [B,T,J], pred_tab [V,J], W [V,J], bias [V]")
-    B, T, J = enc_p.shape
-    V = W.shape[0]
-    if tuple(W.shape) != (V, J) or tuple(pred_tab.shape) != (V, J) or bias.numel() != V:
-        raise ValueError(f"rnnt_beam_decode: pred_tab / W must be [V,J]=[{V},{J}] and bias [V], "
-                         f"got {tuple(pred_tab.shape)}, {tuple(W.shape)}, {tuple(bias.shape)}")
-    if pred_tab.dtype != enc_p.dtype or W.dtype != enc_p.dtype:
-        raise ValueError("rnnt_beam_decode: enc_p, pred_tab and W must share one dtype")
-    if bias.dtype != torch.float32 or not bias.is_contiguous():
-        raise ValueError("rnnt_beam_decode: bias must be contiguous fp32 [V]")
-    if (T > 0 and B > 0 and enc_p.stride(2) != 1) or not pred_tab.is_contiguous() \
-            or not W.is_contiguous():
-        raise ValueError("rnnt_beam_decode: enc_p needs unit inner stride, pred_tab / W contiguous")
-    if mask is not None and (mask.dtype != torch.float32 or tuple(mask.shape) != (B, T)):
-        raise ValueError("rnnt_beam_decode: mask must be fp32 [B, T]")
-    lens = None if lengths is None else _as_len_tensor(lengths, enc_p.device)
-    if lens is not None and lens.numel() != B:
-        raise ValueError("rnnt_beam_decode: lengths must have B entries")
+    B, T, V, J, lens = _joiner_args("rnnt_beam_decode", enc_p, pred_tab, W, bias, lengths, mask)
     if state is None:
         state = RnntBeamState(B, beam, max_symbols, T if max_frames is None else max_frames,
                               enc_p.device)

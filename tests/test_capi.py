@@ -112,6 +112,98 @@ def test_frame_multi_entry_points_reject_bad_arguments_without_gpu(lib):
     assert rc == -1 and b"dtype" in lib.sc_last_error()
 
 
+BEAM_SHAPES = [(1, 1, 1, 0), (3, 5, 2, 7), (2, 32, 8, 100)]   # (B, beam, max_symbols, max_frames)
+
+
+def align8(n):
+    return (n + 7) // 8 * 8
+
+
+@pytest.mark.parametrize("B,beam,ms,max_frames", BEAM_SHAPES)
+def test_beam_state_bytes_are_the_documented_layout(lib, B, beam, ms, max_frames):
+    """Per stream: hdr[4] int32, hash[beam] uint64, the score floats (CTC two, RNN-T one), node,
+    len, last [beam] int32, rounded up to 8 bytes; then the trie of (parent, token) int32 pairs,
+    1 + max_frames * beam (* max_symbols) nodes."""
+    assert lib.sc_ctc_beam_state_bytes(B, beam, max_frames) == \
+        B * (align8(16 + 28 * beam) + 8 * (1 + max_frames * beam))
+    assert lib.sc_rnnt_beam_state_bytes(B, beam, ms, max_frames) == \
+        B * (16 + 24 * beam + 8 * (1 + max_frames * ms * beam))
+
+
+def test_beam_sizes_reject_shapes_that_are_no_state(lib):
+    for beam in (0, 33):
+        assert lib.sc_ctc_beam_state_bytes(2, beam, 10) == 0
+        assert lib.sc_rnnt_beam_state_bytes(2, beam, 2, 10) == 0
+    for ms in (0, 9):
+        assert lib.sc_rnnt_beam_state_bytes(2, 4, ms, 10) == 0
+    assert lib.sc_ctc_beam_state_bytes(2, 4, -1) == 0
+    assert lib.sc_rnnt_beam_state_bytes(2, 4, 2, -1) == 0
+    assert lib.sc_ctc_beam_workspace_bytes(2, 3, 4) == 2 * 3 * 10 * 4
+    assert lib.sc_rnnt_beam_workspace_bytes(2, 37) == 2 * 16 * 37 * 4
+
+
+def test_beam_entry_points_reject_bad_arguments_without_gpu(lib):
+    """sc_ctc_beam_* / sc_rnnt_beam_* reset, frames and result validate before launching (the
+    pointers are never dereferenced), with the messages they have always had."""
+    null, fake = ctypes.c_void_p(), ctypes.c_void_p(0x1000)
+    err = lambda: lib.sc_last_error().decode()   # noqa: E731
+    cn = lib.sc_ctc_beam_state_bytes(1, 4, 10)
+    rn = lib.sc_rnnt_beam_state_bytes(1, 4, 2, 10)
+
+    def ctc_reset(beam=4, nbytes=cn):
+        return lib.sc_ctc_beam_reset(fake, nbytes, 1, beam, 10, null, null)
+
+    def ctc_frames(beam=4, nbytes=cn):
+        return lib.sc_ctc_beam_frames(fake, 0, 1, 1, 5, 8, 40, 8, null, null, 0, 0, 0, beam, 3, fake,
+                                      nbytes, fake, 1 << 20, null)
+
+    def ctc_result(beam=4, nbytes=cn, nbest=1, cap=5):
+        return lib.sc_ctc_beam_result(fake, nbytes, 1, beam, nbest, fake, cap, fake, fake, null, null)
+
+    def rnnt_reset(beam=4, ms=2, nbytes=rn):
+        return lib.sc_rnnt_beam_reset(fake, nbytes, 1, beam, ms, 10, null, null)
+
+    def rnnt_frames(beam=4, ms=2, nbytes=rn):
+        return lib.sc_rnnt_beam_frames(fake, fake, fake, 0, fake, 1, 5, 8, 64, 320, 64, null, null, 0,
+                                       0, 0, beam, 3, ms, fake, nbytes, fake, 1 << 20, null)
+
+    def rnnt_result(beam=4, ms=2, nbytes=rn, nbest=1, cap=5):
+        return lib.sc_rnnt_beam_result(fake, nbytes, 1, beam, ms, nbest, fake, fake, cap, fake, fake,
+                                       null, null)
+
+    for name, fn in (("sc_ctc_beam_reset", ctc_reset), ("sc_ctc_beam_frames", ctc_frames),
+                     ("sc_ctc_beam_result", ctc_result), ("sc_rnnt_beam_reset", rnnt_reset),
+                     ("sc_rnnt_beam_frames", rnnt_frames), ("sc_rnnt_beam_result", rnnt_result)):
+        for beam in (0, 33):
+            assert fn(beam=beam) == -1 and err() == f"{name}: beam={beam} outside [1, 32]"
+        assert fn(nbytes=cn + rn + 4) == -1 and f"{name}: state_bytes={cn + rn + 4} is no" in err()
+    for name, fn in (("sc_rnnt_beam_reset", rnnt_reset), ("sc_rnnt_beam_frames", rnnt_frames),
+                     ("sc_rnnt_beam_result", rnnt_result)):
+        for ms in (0, 9):
+            assert fn(ms=ms) == -1 and err() == f"{name}: max_symbols={ms} outside [1, 8]"
+    for name, fn in (("sc_ctc_beam_result", ctc_result), ("sc_rnnt_beam_result", rnnt_result)):
+        assert fn(nbest=5) == -1 and err() == f"{name}: nbest=5 outside [1, beam=4]"
+        assert fn(nbest=0) == -1 and err() == f"{name}: nbest=0 outside [1, beam=4]"
+        assert fn(cap=-1) == -1 and err() == f"{name}: cap=-1 is negative"
+    # the messages that name the size function and its arguments
+    assert ctc_reset(nbytes=7) == -1 and err() == (
+        f"sc_ctc_beam_reset: state_bytes=7 is not sc_ctc_beam_state_bytes(B=1, beam=4, "
+        f"max_frames=10)={cn}")
+    assert rnnt_reset(nbytes=7) == -1 and err() == (
+        f"sc_rnnt_beam_reset: state_bytes=7 is not sc_rnnt_beam_state_bytes(B=1, beam=4, "
+        f"max_symbols=2, max_frames=10)={rn}")
+    assert ctc_result(nbytes=7) == -1 and err() == (
+        "sc_ctc_beam_result: state_bytes=7 is no sc_ctc_beam_state_bytes(B=1, beam=4, .)")
+    assert rnnt_frames(nbytes=7) == -1 and err() == (
+        "sc_rnnt_beam_frames: state_bytes=7 is no sc_rnnt_beam_state_bytes(B=1, beam=4, "
+        "max_symbols=2, .)")
+    # a state of another decoder's size is no state of this one
+    assert ctc_result(nbytes=rn) == -1 and rnnt_result(nbytes=cn) == -1
+    # empty batches are no-ops
+    assert lib.sc_ctc_beam_reset(null, 0, 0, 4, 10, null, null) == 0
+    assert lib.sc_rnnt_beam_result(null, 0, 0, 4, 2, 1, null, null, 0, null, null, null, null) == 0
+
+
 def test_ctc_side_array_entry_points_reject_bad_arguments_without_gpu(lib):
     """sc_ctc_fwd_ex / sc_ctc_bwd_ex / sc_ctc_split_rows (ABI v10-11) validate before launching:
     emission logits need is_logits and rows of max_target_len + 1; split rows need aligned rows
