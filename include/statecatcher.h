@@ -724,6 +724,7 @@ int64_t sc_mlstm_chunk_state_numel(int BH, int T, int DQ, int DV);
  * the xLSTM layer reads them in place from its fused projection output [B][T][N] (qh = DQ,
  * qt = N) and the backward writes the gradients into the projection's gradient the same way.
  * NULL = contiguous [BH][T][D].  Strides multiples of 8 elements, bases 16-byte aligned.
+ * T == 0: c_last, states_n[:, 0], states_m[:, 0] = the initial state (zeros without one).
  */
 int sc_mlstm_fwd(const void* q, const void* k, const void* v, int dtype, const float* igate,
                  const float* fgate, const float* c0, const float* n0, const float* m0, int BH,
@@ -739,6 +740,9 @@ int sc_mlstm_fwd(const void* q, const void* k, const void* v, int dtype, const f
  * sequence walks the chunks in reverse with dC~ in MFMA accumulators), and the
  * per-step gate terms qdq = q_t.dq_t, kdk = k_t.dk_t (fp32 [BH][T]): d igate = kdk,
  * d fgate_t = sigmoid(-f_t) sum_{r>=t} (qdq_r - kdk_r).  The stabiliser is not differentiated.
+ * With dcT / dnT the final state depends on the last forget gate with no query partner: the
+ * caller adds <dcT, C~_T> + <dnT, n~_T> per sequence to qdq[T-1] before sc_mlstm_gate_bwd
+ * (ops._mlstm_state_grad_term).  T == 0: dstates_C / dstates_n = dcT / dnT (zeros if NULL).
  * layout: as sc_mlstm_fwd's; dq / dk / dv are written with the same strides as q / k / v.
  */
 int sc_mlstm_bwd(const void* q, const void* k, const void* v, int dtype, const float* igate,

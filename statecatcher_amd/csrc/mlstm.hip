@@ -183,6 +183,12 @@ __device__ __forceinline__ float sum16(float x) {
   x = sum8(x);
   return x + dppf<kRowMirror>(0.0f, x);
 }
+// max over aligned groups of 8 lanes (every lane of the group gets it)
+__device__ __forceinline__ float max8(float x) {
+  x = fmaxf(x, dppf<kQuadX1>(x, x));
+  x = fmaxf(x, dppf<kQuadX2>(x, x));
+  return fmaxf(x, dppf<kHalfMirror>(x, x));
+}
 __device__ __forceinline__ float wave_max(float x) {
   x = fmaxf(x, dppf<kQuadX1>(x, x));
   x = fmaxf(x, dppf<kQuadX2>(x, x));
@@ -810,7 +816,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
   __shared__ __attribute__((aligned(16))) T dA[kL * LL];
   __shared__ __attribute__((aligned(16))) T Am[kL * LL];
   __shared__ float sb[kL], si[kL], mt[kL], rowf[kL], es[kL], dden[kL], nk[DQ], dnk[DQ];
-  __shared__ float part[NI * kL], dnp[4 * DQ], smax[16];
+  __shared__ float part[NI * kL], dnp[4 * DQ], smax[16], irow[kL], ddr[kL];
   constexpr int NQ8 = kL * DQ / 8, NV8 = kL * DV / 8, NC8 = DQ * DV / 8;
   constexpr int UQ = (NQ8 + 511) / 512, UV = (NV8 + 511) / 512, UC = (NC8 + 511) / 512;
   constexpr int UH = DV / 64;   // dh / h pieces per thread (8 threads per row)
@@ -879,6 +885,19 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     }
   };
   // gate quantities (every wave, lane = step) and the Q / K (/ Qr) / V fill; returns g = b_{L-1}
+  // f16 row factors.  Two per-row factors span e^{+-25} over a chunk's rows once the gates sit at
+  // the soft cap: rowf_t = s e^{b_t + m_k - m_t} (5e-8 after one input gate of 15) and dnum's
+  // 1 / z_t (one near-cancelling row at the floor e^{-m_t} sets the chunk scale and leaves every
+  // other row of dh / z at 1e-7 of it); their products are moderate.  f16 images that carry one of
+  // them alone lose the small rows -- all of the gradient w.r.t. a chunk's incoming state, so of
+  // the initial state, in that regime.  So row t of the f16 image Dn holds dh_t f_t 2^-d_t, with
+  // f_t in [0.5, 1) the mantissa of S_k / z_t = f_t 2^{e_t} and 2^-d_t the power of two that takes
+  // the row's largest |dh_t| to [0.5, 1): every row at dh's own precision.  The remaining power of
+  // two irow_t = 2^{e_t + d_t} <= 2 (dnum_t S_k = Dn_t irow_t; 0 for a row without dh) joins the
+  // other side of each product in fp32 before that side is rounded: the rows of A for dv, rowf for the state update (Qr = diag(rowf irow qrP) Q, qrP
+  // the power of two that takes the largest rowf_t irow_t to [0.5, 1), taken out of the fp32
+  // carry again), and the accumulators of Dn V^T and Dn C~^T directly.  All exact scalings.
+  float qrP = 1.0f, qrI = 1.0f;
   auto fill_chunk = [&](bool with_qr) __attribute__((always_inline)) {
     const float b = wave_prefix_sum(logsig(g_f), lane);
     const float rowf_l = a.scale * expf(b + mk - g_m);
@@ -895,7 +914,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
         const V8 x = cvt8<DT, IO>(rq[u]);
         *(V8*)(Qs + r * LQ + c) = x;
         *(V8*)(Ks + r * LQ + c) = cvt8<DT, IO>(rk[u]);
-        if (with_qr) {
+        if (with_qr && !kScale) {   // (f16: fill_qr, once irow is known)
           V8 y;
 #pragma unroll
           for (int j = 0; j < 8; ++j) y[j] = (T)((float)x[j] * f);
@@ -954,6 +973,23 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
   auto fill_dn = [&](float z, float Sk) __attribute__((always_inline)) {
     const int t = tid >> 3, pt = tid & 7;
     const float zs = Sk / z;
+    float zf = zs, ir = 1.0f;   // the factor in the image, and what it leaves out (f16)
+    if constexpr (kScale) {
+      float rm = 0.0f;   // the row's largest |dh|
+#pragma unroll
+      for (int u = 0; u < UH; ++u) {
+        const V8I xd = __builtin_bit_cast(V8I, rd[u]);
+#pragma unroll
+        for (int e2 = 0; e2 < 8; ++e2) rm = fmaxf(rm, fabsf((float)xd[e2]));
+      }
+      rm = max8(rm);
+      const bool okr = rm > 0.0f && rm < 3.0e38f, okz = zs > 0.0f && zs < 3.0e38f;
+      int ez = 0, ed = 0;
+      const float f = okz ? frexpf(zs, &ez) : 0.0f;
+      if (okr) frexpf(rm, &ed);
+      zf = okr ? ldexpf(f, -ed) : 0.0f;                    // dh zf in [0.25, 1) at the row's largest
+      ir = okr && okz ? ldexpf(1.0f, ez + ed) : 0.0f;      // <= 2: S_k |dh_t| / z_t < 1 (chunk_scale)
+    }
     float dot = 0.0f;
 #pragma unroll
     for (int u = 0; u < UH; ++u) {
@@ -964,7 +1000,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
       for (int e2 = 0; e2 < 8; ++e2) {
         const float d = (float)xd[e2];
         dot += d * (float)xh[e2];
-        o[e2] = (T)(d * zs);
+        o[e2] = (T)(d * zf);
       }
       *(V8*)(Dn + t * LV + pt * 8 + 64 * u) = o;
     }
@@ -973,6 +1009,10 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
       const float live = fabsf(dv_) >= expf(-m_t) ? 1.0f : 0.0f;
       dden[t] = -dot * zs * (dv_ >= 0.0f ? 1.0f : -1.0f) * live;
       mt[t] = m_t;
+      if constexpr (kScale) {
+        irow[t] = ir;
+        ddr[t] = -dot * zf * (dv_ >= 0.0f ? 1.0f : -1.0f) * live;   // dden / irow, for Qr
+      }
     }
   };
   // one causal 16 x 16 tile of A = W o (Q K^T) (isA) or dA = W o (Dn V^T + dden)
@@ -1005,8 +1045,9 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     for (int r = 0; r < 4; ++r) {
       const int tt = 16 * tr + 4 * (lane >> 4) + r;
       const float wts = (s <= tt) ? a.scale * expf(sb[tt] - sb[s] + si[s] - mt[tt]) : 0.0f;
-      if (isA) Am[tt * LL + s] = (T)(c4[r] * wts);
-      else dA[tt * LL + s] = (T)((c4[r] + dden[tt]) * wts);
+      const float ir = kScale ? irow[tt] : 1.0f;
+      if (isA) Am[tt * LL + s] = (T)(c4[r] * wts * ir);
+      else dA[tt * LL + s] = (T)((c4[r] * ir + dden[tt]) * wts);
     }
   };
 
@@ -1083,7 +1124,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int tt = 16 * tr + 4 * (lane >> 4) + r;
-            const float v = d4[c][r] + rowf[tt] * (e4[c][r] + dden[tt] * nki);
+            const float v = d4[c][r] + rowf[tt] * (e4[c][r] * (kScale ? irow[tt] : 1.0f) + dden[tt] * nki);
             dQg[(t0 + tt) * a.qt + i] = out16<DT, IO>(v * inv);
             qd[r] = sum16(v * (float)Qs[tt * LQ + i]);
           }
@@ -1171,10 +1212,36 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
       *(v4t*)(CS + (j0 + (lane & 15)) * LQ + i0 + 4 * (lane >> 4)) = c;
     }
     __syncthreads();
+    float fq = 0.0f;
+    if constexpr (kScale) {   // Qr = diag(rowf irow qrP) Q (see the f16 row factors above)
+      const float fr = rowf[lane] * irow[lane];
+      const float mr = wave_max(fr);
+      int ex = 0;
+      if (mr > 0.0f && mr < 3.0e38f) frexpf(mr, &ex);
+      ex = ex > 60 ? 60 : ex < -60 ? -60 : ex;   // (the carry times qrP stays finite)
+      qrP = ldexpf(1.0f, -ex);
+      qrI = ldexpf(1.0f, ex);
+      fq = fr * qrP;
+    }
     if (k > 0) load_rows(k - 1);   // dh / h of this chunk are consumed
     // ---- A = W o (Q K^T) and dA = W o (Dn V^T + dden): 10 causal tiles each, 20 jobs ----
 #pragma unroll 1
     for (int jb = w; jb < 20; jb += 8) a_job(jb < 10 ? jb : jb - 10, jb < 10);
+    if constexpr (kScale) {
+      // (waves 4 .. 7 have two of the 20 jobs where waves 0 .. 3 have three: they write Qr)
+      static_assert(NQ8 % 256 == 0, "Qr pieces over four waves");
+      if (w >= 4) {
+        for (int e = tid - 256; e < NQ8; e += 256) {
+          const int r = e / (DQ / 8), c = (e % (DQ / 8)) * 8;
+          const float f = __shfl(fq, r & 63);
+          const V8 x = *(const V8*)(Qs + r * LQ + c);
+          V8 y;
+#pragma unroll
+          for (int j = 0; j < 8; ++j) y[j] = (T)((float)x[j] * f);
+          *(V8*)(Qr + r * LQ + c) = y;
+        }
+      }
+    }
     __syncthreads();
     if (k > 0) load_qkv(k - 1);
     const float inv = 1.0f / S;
@@ -1256,7 +1323,7 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
     }
     // ---- state gradient to the chunk start: dC~_k = decay dC~_{k+1} + Qr^T Dn ----
 #pragma unroll
-    for (int p = 0; p < PC; ++p) acc[p] *= decay;
+    for (int p = 0; p < PC; ++p) acc[p] *= kScale ? decay * qrP : decay;   // (Qr carries qrP)
 #pragma unroll
     for (int kk = 0; kk < kL / 32; ++kk) {
       V8 fq[BI], fd[BJ];
@@ -1267,6 +1334,10 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
       for (int p = 0; p < PC; ++p) acc[p] = M::mma(fq[p / BJ], fd[p % BJ], acc[p]);
     }
+    if constexpr (kScale) {
+#pragma unroll
+      for (int p = 0; p < PC; ++p) acc[p] *= qrI;
+    }
     // dn~ partial sums sum_t dden_t Qr[t][i] over four 16-step quarters (combined next chunk)
     if (tid < 4 * DQ) {
       const int i = tid % DQ, qt4 = tid / DQ;
@@ -1274,9 +1345,9 @@ __global__ void __launch_bounds__(512, 1) mlstm_bw_walk(MArgs a) {
 #pragma unroll
       for (int u = 0; u < 16; ++u) {
         const int tt = 16 * qt4 + u;
-        sacc += dden[tt] * (float)Qr[tt * LQ + i];
+        sacc += (kScale ? ddr[tt] : dden[tt]) * (float)Qr[tt * LQ + i];
       }
-      dnp[qt4 * DQ + i] = sacc;
+      dnp[qt4 * DQ + i] = kScale ? sacc * qrI : sacc;
     }
     __syncthreads();
     if (tid < kL) {   // (part comes from every wave's dk jobs: after the barrier)
@@ -1448,6 +1519,19 @@ __global__ void __launch_bounds__(64) mlstm_gate_bwd_kernel(GateArgs g) {
   }
 }
 
+// T == 0: there is no chunk to walk, so a state (or a state gradient) passes through unchanged:
+// dst = src, or zeros without one
+__global__ void __launch_bounds__(256) mlstm_pass_state_kernel(float* dst, const float* src,
+                                                               int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+    dst[i] = src ? src[i] : 0.0f;
+}
+void pass_state(float* dst, const float* src, int64_t n, hipStream_t st) {
+  const int64_t blocks = (n + 255) / 256;
+  hipLaunchKernelGGL(mlstm_pass_state_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)),
+                     dim3(256), 0, st, dst, src, n);
+}
+
 }  // namespace
 
 }  // namespace sc
@@ -1477,7 +1561,15 @@ extern "C" int sc_mlstm_fwd_io(const void* q, const void* k, const void* v, int 
   SC_REQUIRE(BH >= 0 && T >= 0, "sc_mlstm_fwd: bad shape");
   SC_REQUIRE(T % kL == 0, "sc_mlstm_fwd: T=%d is not a multiple of the chunk length %d", T, kL);
   SC_REQUIRE(dims_supported(DQ, DV), "sc_mlstm_fwd: head dims (%d, %d) not compiled in", DQ, DV);
-  if (BH == 0 || T == 0) return 0;
+  if (BH == 0) return 0;
+  if (T == 0) {   // the final state is the initial state (zeros without one)
+    SC_REQUIRE(states_n && states_m && c_last, "sc_mlstm_fwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    pass_state(c_last, c0, (int64_t)BH * DQ * DV, st);
+    pass_state(states_n, n0, (int64_t)BH * DQ, st);
+    pass_state(states_m, m0, BH, st);
+    return launch_status("sc_mlstm_fwd");
+  }
   SC_REQUIRE(q && k && v && igate && fgate && h && states_C && states_n && states_m && c_last &&
                  m_rows && den_rows,
              "sc_mlstm_fwd: null pointer");
@@ -1517,7 +1609,14 @@ extern "C" int sc_mlstm_bwd_io(const void* q, const void* k, const void* v, int 
              io_dtype);
   SC_REQUIRE(T % kL == 0, "sc_mlstm_bwd: T=%d is not a multiple of the chunk length %d", T, kL);
   SC_REQUIRE(dims_supported(DQ, DV), "sc_mlstm_bwd: head dims (%d, %d) not compiled in", DQ, DV);
-  if (BH == 0 || T == 0) return 0;
+  if (BH == 0) return 0;
+  if (T == 0) {   // the initial state's gradient is the final state's (zeros without one)
+    SC_REQUIRE(dstates_C && dstates_n, "sc_mlstm_bwd: null pointer");
+    hipStream_t st = (hipStream_t)stream;
+    pass_state(dstates_C, dcT, (int64_t)BH * DQ * DV, st);
+    pass_state(dstates_n, dnT, (int64_t)BH * DQ, st);
+    return launch_status("sc_mlstm_bwd");
+  }
   SC_REQUIRE(q && k && v && igate && fgate && h && dh && states_C && states_n && states_m &&
                  m_rows && den_rows && dstates_C && dstates_n && dq && dk && dv && qdq && kdk,
              "sc_mlstm_bwd: null pointer");

@@ -1885,8 +1885,28 @@ def _mlstm_fp32_cell(q, k, v):
     where it cannot, the range-safe bf16 cell is used."""
     if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
         return torch.bfloat16
+    if q.numel() == 0 or v.numel() == 0:
+        return torch.float16
     m = torch.stack([q.abs().amax(), k.abs().amax(), v.abs().amax()]).amax()
     return torch.float16 if bool(m <= _F16_MAX) else torch.bfloat16
+
+
+def _mlstm_state_grad_term(qdq, T, dcT, cT, dnT, nT):
+    """The final state's own dependence on the last forget gate.  C~_T = sum_s e^{F_T - F_s + i_s
+    - m_T} k_s v_s^T + e^{F_T + m_0 - m_T} C~_0 (n~_T alike) carries F_T with no query partner,
+    so the pair identity dF_t = q_t.dq_t - k_t.dk_t misses <dC_T, C~_T> + <dn_T, n~_T> at
+    t = T - 1: it is added to qdq there, per sequence, before sc_mlstm_gate_bwd's reverse
+    cumulative sum.  Only when a state gradient arrives: with detached carried states (the
+    training path) qdq is untouched."""
+    if T == 0 or (dcT is None and dnT is None):
+        return
+    term = None
+    if dcT is not None:
+        term = (dcT.float() * cT).flatten(2).sum(-1)
+    if dnT is not None:
+        tn = (dnT.float() * nT).sum(-1)
+        term = tn if term is None else term + tn
+    qdq[:, T - 1] += term.reshape(-1)
 
 
 class MLSTMFn(torch.autograd.Function):
@@ -1912,7 +1932,7 @@ class MLSTMFn(torch.autograd.Function):
         if T % 64:
             raise ValueError(f"T={T} must be a multiple of 64 (the reference pads to 64)")
         BH, nc = B * NH, T // 64
-        qc, kc, vc = (x.to(cdt).contiguous().view(BH, T, -1) for x in (q, k, v))
+        qc, kc, vc = (x.to(cdt).contiguous().view(BH, T, x.shape[-1]) for x in (q, k, v))
         ig = igate.float().contiguous().view(BH, T)
         fg = fgate.float().contiguous().view(BH, T)
         c0c = None if c0 is None else c0.float().contiguous()
@@ -1933,7 +1953,7 @@ class MLSTMFn(torch.autograd.Function):
                                   ptr(ns), ptr(ms), ptr(cT), ptr(mrow), ptr(den), None,
                                   stream_of(qc))
         check(rc, "sc_mlstm_fwd")
-        ctx.save_for_backward(qc, kc, vc, ig, fg, h, Cs, ns, ms, mrow, den)
+        ctx.save_for_backward(qc, kc, vc, ig, fg, h, Cs, ns, ms, mrow, den, cT)
         ctx.meta = (B, NH, T, DQ, DV, float(eps), q.dtype, k.dtype, v.dtype, c0 is not None,
                     n0 is not None)
         nT = ns[:, nc].view(B, NH, DQ).clone()
@@ -1943,7 +1963,7 @@ class MLSTMFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dh, dcT, dnT, dmT):
-        qc, kc, vc, ig, fg, h, Cs, ns, ms, mrow, den = ctx.saved_tensors
+        qc, kc, vc, ig, fg, h, Cs, ns, ms, mrow, den, cT = ctx.saved_tensors
         B, NH, T, DQ, DV, eps, qdt, kdt, vdt, has_c0, has_n0 = ctx.meta
         BH, nc = B * NH, T // 64
         dev = qc.device
@@ -1968,6 +1988,7 @@ class MLSTMFn(torch.autograd.Function):
                 eps, ptr(dCs), ptr(dns), ptr(dq), ptr(dk), ptr(dv), ptr(qdq), ptr(kdk), None,
                 stream_of(qc))
         check(rc, "sc_mlstm_bwd")
+        _mlstm_state_grad_term(qdq, T, dcTc, cT, dnTc, ns[:, nc].view(B, NH, DQ))
         # d igate_s = k_s.dk_s ; dF_t = q_t.dq_t - k_t.dk_t ; d fgate = sigmoid(-f) revcumsum(dF)
         dfg = torch.empty_like(kdk)
         check(_lib.load().sc_mlstm_gate_bwd(ptr(qdq), ptr(kdk), ptr(fg), BH, T, ptr(dfg), None, None,
@@ -2054,7 +2075,7 @@ class MLSTMCoreFn(torch.autograd.Function):
         mh_fwd = lib.sc_mhln_gate_fwd_h16 if h.dtype == torch.float16 else lib.sc_mhln_gate_fwd
         check(mh_fwd(ptr(h), base + oo * esz, N, ptr(wf), ptr(y), ptr(mean), ptr(rstd),
                      B, T, NH, DV, float(eps_mh), stream), "sc_mhln_gate_fwd")
-        ctx.save_for_backward(a, ig, fg, h, Cs, ns, ms, mrow, den, wf, mean, rstd)
+        ctx.save_for_backward(a, ig, fg, h, Cs, ns, ms, mrow, den, wf, mean, rstd, cT)
         ctx.meta = (NH, DQ, DV, cap, float(eps), c0 is not None, n0 is not None, w_mh.dtype)
         nT = ns[:, nc].view(B, NH, DQ).clone()
         mT = ms[:, nc].view(B, NH, 1).clone()
@@ -2063,7 +2084,7 @@ class MLSTMCoreFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy, dcT, dnT, dmT):
-        a, ig, fg, h, Cs, ns, ms, mrow, den, wf, mean, rstd = ctx.saved_tensors
+        a, ig, fg, h, Cs, ns, ms, mrow, den, wf, mean, rstd, cT = ctx.saved_tensors
         NH, DQ, DV, cap, eps, has_c0, has_n0, wdt = ctx.meta
         B, T, N = a.shape
         BH, nc = B * NH, T // 64
@@ -2103,6 +2124,7 @@ class MLSTMCoreFn(torch.autograd.Function):
                 ptr(den), BH, T, DQ, DV, eps, ptr(dCs), ptr(dns), dbase + qo * esz,
                 dbase + ko * esz, dbase + vo * esz, ptr(qdq), ptr(kdk), lay, stream)
         check(rc, "sc_mlstm_bwd")
+        _mlstm_state_grad_term(qdq, T, dcTc, cT, dnTc, ns[:, nc].view(B, NH, DQ))
         # gate gradients as MLSTMFn returns them, then through the soft caps (fp32, one bf16
         # rounding; _soft_cap_bwd's torch chain rounds each op) straight into da: one kernel
         check(lib.sc_mlstm_gate_bwd(ptr(qdq), ptr(kdk), ptr(fg), BH, T, None, base, dbase, NH, N,

@@ -135,7 +135,7 @@ def _mean_backward(ctx, grad_loss, grad_factor):
 def _mlstm_setup(ctx, inputs, output):
     q, k, v, ig, fg, c0, n0, m0, eps = inputs
     h, c_last, ns, ms, cs, mrow, den = output
-    ctx.save_for_backward(q, k, v, ig, fg, h, cs, ns, ms, mrow, den)
+    ctx.save_for_backward(q, k, v, ig, fg, h, cs, ns, ms, mrow, den, c_last)
     ctx.eps = eps
     ctx.has = (c0 is not None, n0 is not None)
     ctx.nc = ns.shape[1] - 1
@@ -144,12 +144,23 @@ def _mlstm_setup(ctx, inputs, output):
 def _mlstm_backward(ctx, dh, dc_last, dns, dms, dcs, dmrow, dden):
     """Gradients of (h, final C, final n) -- the n / m state outputs beyond the final chunk are
     internal (their gradients are ignored, as the stabiliser is not differentiated)."""
-    q, k, v, ig, fg, h, cs, ns, ms, mrow, den = ctx.saved_tensors
+    q, k, v, ig, fg, h, cs, ns, ms, mrow, den, c_last = ctx.saved_tensors
+    B, NH, T = q.shape[:3]
     if dh is None:
         dh = torch.zeros_like(h)
-    dn_last = None if dns is None else dns[:, ctx.nc].reshape(q.shape[0], q.shape[1], -1)
+    dn_last = None if dns is None else dns[:, ctx.nc].reshape(B, NH, -1)
     dq, dk, dv, dc0, dn0, qdq, kdk = torch.ops.statecatcher.mlstm_bwd(
         q, k, v, ig, fg, h, dh, dc_last, dn_last, cs, ns, ms, mrow, den, ctx.eps)
+    # the final state depends on the last forget gate with no query partner: <dC_T, C~_T> +
+    # <dn_T, n~_T> joins q.dq - k.dk at T - 1 (ops._mlstm_state_grad_term), only when a state
+    # gradient arrives
+    if T > 0 and (dc_last is not None or dn_last is not None):
+        term = 0.0
+        if dc_last is not None:
+            term = (dc_last.float() * c_last).flatten(2).sum(-1)
+        if dn_last is not None:
+            term = term + (dn_last.float() * ns[:, ctx.nc].reshape(B, NH, -1)).sum(-1)
+        qdq = torch.cat([qdq[..., :-1], qdq[..., -1:] + term.reshape(B, NH, 1)], -1)
     # d igate_s = k_s.dk_s ; d fgate_t = sigmoid(-f_t) sum_{r >= t} (q_r.dq_r - k_r.dk_r)
     dfg = torch.ops.statecatcher.mlstm_gate_bwd(qdq, kdk, fg)
     has_c0, has_n0 = ctx.has
