@@ -58,8 +58,37 @@ extern "C" {
 #define SC_BF16 1
 #define SC_F16 2
 
-/* ABI version; bumped on any signature change */
+/*
+ * Every `#define SC_NAME <integer>` and every declaration below is also read by the Python
+ * binding (statecatcher_amd/_lib.py parses this file at import): keep to int, int64_t, size_t,
+ * float, double and pointers.
+ */
+
+/* sc_abi_version() returns SC_ABI_VERSION; bump it on any signature or struct change (the
+ * binding refuses a library built from another version of this file) */
+#define SC_ABI_VERSION 14
 int sc_abi_version(void);
+
+/* most jobs one call takes: sc_lucy_frame_gemm_multi / _cellb_multi / sc_lucy_tframe_layer_multi,
+ * sc_weight_images, sc_ln_fold_prep (callers with more split the list) */
+#define SC_MAX_FRAME_JOBS 8
+#define SC_MAX_IMAGE_JOBS 16
+#define SC_MAX_FOLD_JOBS 16
+
+/* sc_lucy_frame_gemm's epi */
+#define SC_FRAME_PLAIN 0
+#define SC_FRAME_STATS 1
+#define SC_FRAME_CELL_UNFUSED 2
+#define SC_FRAME_CELL_FUSED 3
+
+/* sc_lucy_step_cell's mode */
+#define SC_STEP_FUSED 0
+#define SC_STEP_UNFUSED_A 1
+#define SC_STEP_UNFUSED_B 2
+
+/* sc_fbank's kind */
+#define SC_FBANK_MFCC 0
+#define SC_FBANK_MEL 1
 
 /* Message for the last SC_EINVAL / launch failure on this thread ("" if none). */
 const char* sc_last_error(void);
@@ -222,7 +251,7 @@ int sc_layernorm_bwd(const void* x, const void* dy, int dtype, const float* gamm
 /*
  * The LayerNorm fold around the scans (see sc_lucy_scan_fwd_ln).  Per job (one gate projection
  * W fp32 [rows = 7D][ld], the preceding LayerNorm's gamma / beta [D], the projection bias [rows]
- * or NULL), in one launch for up to 16 jobs:
+ * or NULL), in one launch for up to SC_MAX_FOLD_JOBS jobs:
  *   shift[n] = mean_k gamma_k W_nk   (row_shift of the W'' image; W''_nk = bf16(gamma_k W_nk -
  *                                     shift_n), computed unfused, as sc_weight_images computes it)
  *   bias_out[n] = b_n + sum_k W_nk beta_k
@@ -381,14 +410,14 @@ int sc_lucy_step_ln(const void* x, int dtype, const float* w, const float* b, fl
                     int B, int D, void* stream);
 
 /*
- * mode 0 (fused_ops, :47-54):  g = [z | k | v | h_pre | decay_logits] (5D per row; the
+ * mode SC_STEP_FUSED (fused_ops, :47-54):  g = [z | k | v | h_pre | decay_logits] (5D per row; the
  *   reference's r chunk is computed and never used, so the caller drops W_fused's first D rows);
  *   s' = sigmoid(dl) s + k v;  c = tanh(LN_h(h_pre + s'));  h' = (1 - z~) c + z~ h with
  *   z~ = sigmoid(LN_z(z));  masked blend (:66-68) with mask[b];  out = new h.
- * mode 1 (unfused, :55-60):  g = [W_z u | W_k u | W_v u | W_decay u];  s updated as above;
- *   out = u + s' (the input of W_h).
- * mode 2 (unfused, :61-68):  hp = W_h(u + s');  c = tanh(LN_h(hp));  z~ from g as in mode 0;
- *   h updated and masked;  out = new h.
+ * mode SC_STEP_UNFUSED_A (unfused, :55-60):  g = [W_z u | W_k u | W_v u | W_decay u];  s updated
+ *   as above;  out = u + s' (the input of W_h).
+ * mode SC_STEP_UNFUSED_B (unfused, :61-68):  hp = W_h(u + s');  c = tanh(LN_h(hp));  z~ from g as
+ *   in the fused mode;  h updated and masked;  out = new h.
  * LayerNorm pointers null = layer_norm False (nn.Identity).  mask: fp32 [B] or null.
  */
 int sc_lucy_step_cell(int mode, const void* g, int dtype, int64_t g_stride, const void* u,
@@ -403,11 +432,15 @@ int sc_lucy_step_cell(int mode, const void* g, int dtype, int64_t g_stride, cons
  *
  * sc_lucy_frame_gemm: y[b][j] = sum_k x~[b][k] w[j][k] + bias[j], x~ = x or, when ln_w is given,
  *   LayerNorm(x) from the nst_in records of st_in (lucyrnn.py:45 layernorm_in).  epi:
- *   0 plain; 1 plain + one statistics record of y per 32 columns into st_out ([ceil(N/32)][B]);
- *   2 unfused gates (N = 4D: z k v decay, lucyrnn.py:55-59): s' = sigmoid(decay) s + k v into s
- *     (masked), y = x~ + s' ([B][D], K == D), z ([B][D]), records of z per 16 units into st_z;
- *   3 fused gates (N = 5D: z k v h_pre decay; W_fused without its unused r rows, :47-53): s as
- *     above, y = h_pre + s', z, records of y into st_out and of z into st_z ([D/16][B] each).
+ *   SC_FRAME_PLAIN  plain;
+ *   SC_FRAME_STATS  plain + one statistics record of y per 32 columns into st_out
+ *     ([ceil(N/32)][B]);
+ *   SC_FRAME_CELL_UNFUSED  unfused gates (N = 4D: z k v decay, lucyrnn.py:55-59): s' =
+ *     sigmoid(decay) s + k v into s (masked), y = x~ + s' ([B][D], K == D), z ([B][D]), records of
+ *     z per 16 units into st_z;
+ *   SC_FRAME_CELL_FUSED  fused gates (N = 5D: z k v h_pre decay; W_fused without its unused r
+ *     rows, :47-53): s as above, y = h_pre + s', z, records of y into st_out and of z into st_z
+ *     ([D/16][B] each).
  *   x 16-byte aligned with ldx % 4 == 0, K % 4 == 0; w 16-byte aligned with ldw % 8 == 0.
  * sc_lucy_frame_cellb: h = (1 - sigmoid(LN_z z)) tanh(LN_h hp) + sigmoid(LN_z z) h (masked,
  *   :61-68) in place, and out[b][:D] = h (the next layer's input).
@@ -423,11 +456,11 @@ int sc_lucy_frame_cellb(const float* z, const void* st_z, int nst_z, const float
                         int64_t ldo, const float* mask, int B, int D, void* stream);
 
 /*
- * The same two kernels over up to 8 independent jobs in ONE launch each: a block of F frames of
- * an L-layer model runs as a wavefront over (frame, layer) -- stage tau computes layer l of frame
- * tau - l for every l at once, since layer l of frame j needs only layer l - 1 of frame j and
- * layer l of frame j - 1 -- so a block takes 4 (F + L - 1) launches instead of 4 F L (statecatcher
- * _amd/streaming.py).  Each job has the arguments of one sc_lucy_frame_gemm / _cellb call; the
+ * The same two kernels over up to SC_MAX_FRAME_JOBS independent jobs in ONE launch each: a block
+ * of F frames of an L-layer model runs as a wavefront over (frame, layer) -- stage tau computes
+ * layer l of frame tau - l for every l at once, since layer l of frame j needs only layer l - 1 of
+ * frame j and layer l of frame j - 1 -- so a block takes 4 (F + L - 1) launches instead of 4 F L
+ * (statecatcher_amd/streaming.py).  Each job has the arguments of one sc_lucy_frame_gemm / _cellb call; the
  * jobs of one call share epi, w_dtype, eps and the presence of the LayerNorm prologue.
  */
 typedef struct sc_frame_gemm_job {
@@ -488,9 +521,10 @@ int sc_lucy_frame_cellb_multi(float eps, const sc_frame_cell_job* jobs, int njob
  * ldx % 4 == 0, ldw % 8 == 0, both >= K; ln_w, ln_b and st_in together or not at all.  B == 0 is
  * a no-op.  No allocation, no atomics: captures into a HIP graph.
  *
- * sc_lucy_tframe_layer_multi: up to 8 such jobs in one launch (blockIdx.z = job), sharing w_dtype
- * and eps; jobs with and without the prologue may mix (layer 0 has none).  A block of F frames of
- * an L-layer model is then F + L - 1 launches: stage tau = layer l of frame tau - l for every l.
+ * sc_lucy_tframe_layer_multi: up to SC_MAX_FRAME_JOBS such jobs in one launch (blockIdx.z = job),
+ * sharing w_dtype and eps; jobs with and without the prologue may mix (layer 0 has none).  A
+ * block of F frames of an L-layer model is then F + L - 1 launches: stage tau = layer l of frame
+ * tau - l for every l.
  * Within a launch the jobs run concurrently, so the caller double-buffers each layer's out /
  * st_out (the job of layer l - 1 writes frame j + 1 while layer l reads frame j).
  */
@@ -609,9 +643,9 @@ int sc_adam_step(const sc_adam_tensor* t, int nt, const float* part, int64_t npa
                  float* norm_out, void* stream);
 
 /*
- * Per-step bf16 images of the fp32 projection weights, one launch for up to 16 weights: the
- * autocast casts of LinearSafe (lucyrnn_triton.py:20-25 under train.py's autocast) plus the
- * layouts the GEMMs want.  Per job: dst bf16 [rows][cols_pad] = src rows (stride ld_src) with
+ * Per-step bf16 images of the fp32 projection weights, one launch for up to SC_MAX_IMAGE_JOBS
+ * weights: the autocast casts of LinearSafe (lucyrnn_triton.py:20-25 under train.py's autocast)
+ * plus the layouts the GEMMs want.  Per job: dst bf16 [rows][cols_pad] = src rows (stride ld_src) with
  * zero columns cols..cols_pad-1, rows in step-blocked order (block, gate, unit) when block_d = D
  * > 0 (rows = 7 D, D % 64 == 0; dst row (b, g, u) = src row g D + 64 b + u); dst_t (optional)
  * bf16 [cols][rows] = dst's first cols columns transposed.  Round to nearest even.
@@ -689,10 +723,10 @@ size_t sc_fbank_workspace_bytes(void);
  * audio fp32 [B][audio_stride] (n_samples used per row) -> out fp32 [B][frames][80].
  * n_fft = win = 400 (periodic Hann), hop 160, center=False, power 2, 80 HTK mel bands over
  * [0, sample_rate/2], no filter normalisation.
- *   kind 0 (mfcc): log(mel + 1e-6), orthonormal DCT-II, 80 coefficients;
- *   kind 1 (mel):  10 log10(max(mel, 1e-10)), then max(x, max over the whole call - 80)
+ *   kind SC_FBANK_MFCC: log(mel + 1e-6), orthonormal DCT-II, 80 coefficients;
+ *   kind SC_FBANK_MEL:  10 log10(max(mel, 1e-10)), then max(x, max over the whole call - 80)
  *                  (AmplitudeToDB(top_db=80) on a (B, 80, frames) spectrogram).
- * workspace: sc_fbank_workspace_bytes() device bytes (kind 1 only).
+ * workspace: sc_fbank_workspace_bytes() device bytes (SC_FBANK_MEL only).
  */
 int sc_fbank(const float* audio, int B, int64_t n_samples, int64_t audio_stride, int kind,
              float sample_rate, float* out, void* workspace, size_t workspace_bytes, void* stream);

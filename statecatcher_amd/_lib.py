@@ -1,202 +1,115 @@
 """ctypes binding of libstatecatcher_hip.so (C ABI: include/statecatcher.h).
 
+The header is the one definition of the ABI: every prototype, job struct and `#define SC_*` integer
+is read from it at import, so the binding cannot drift from what the library was compiled against.
+
 The product path has no CPU fallback: every op raises if the library is missing, if a tensor is
 not on a ROCm device, or if a call returns a non-zero status.
 """
 import ctypes
 import os
+import re
 
 import torch  # noqa: F401  (loads torch's HIP runtime first: our .so binds to the same SONAME)
 
+_HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_NAME = "libstatecatcher_hip.so"
 # SC_LIB_PATH: load another build of the same ABI (ablation builds under tools/); default in-tree
-LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
-                                                         LIB_NAME)
+LIB_PATH = os.environ.get("SC_LIB_PATH") or os.path.join(_HERE, LIB_NAME)
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "statecatcher.h")
 
-SC_F32, SC_BF16, SC_F16 = 0, 1, 2
-_DTYPE = {torch.float32: SC_F32, torch.bfloat16: SC_BF16, torch.float16: SC_F16}
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char *": ctypes.c_char_p})
+_POINTEES = set(_SCALARS) | {"void", "char", "int32_t"}   # and the header's own structs
+_STRUCT = re.compile(r"typedef\s+struct\s*(\w*)\s*\{([^{}]*)\}\s*(\w+)\s*;")
+_PROTO = re.compile(r"(\w[\w\s*]*?)\b(\w+)\s*\(([^(){};]*)\)\s*;")
+_DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(SC_\w+)\b(.*)$", re.M)
+_SPACE = re.compile(r"\s*")
+_INTEGER = re.compile(r"\s*(?:(-?\d+)|\(\s*(-?\d+)\s*\))\s*")
 
-_c = ctypes
-_i32, _i64, _vp, _fp = _c.c_int, _c.c_int64, _c.c_void_p, _c.c_void_p
-ABI_VERSION = 14  # include/statecatcher.h; bumped on any signature change
 
-_SIGS = {
-    "sc_abi_version": (_i32, []),
-    "sc_gemm_wgrad_splits": (_i32, [_i32, _i32, _i32]),
-    "sc_gemm_wgrad_bf16": (_i32, [_vp, _i64, _vp, _i64, _fp, _i32, _i32, _i32, _i32, _vp]),
-    "sc_gemm_tn_bf16": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp]),
-    "sc_gemm_tn_ln_bf16": (_i32, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _fp, _vp,
-                                 _c.c_float, _vp]),
-    "sc_last_error": (_c.c_char_p, []),
-    "sc_lucy_scan_chunk": (_i32, []),
-    "sc_lucy_scan_ckpt_numel": (_i64, [_i32, _i32, _i32]),
-    "sc_lucy_scan_fwd": (_i32, [_vp, _i32, _fp, _fp, _fp, _vp, _fp, _fp, _i32, _i32, _i32,
-                               _i64, _i64, _i64, _i64, _i64, _i64, _fp, _vp]),
-    "sc_lucy_scan_fwd_split": (_i32, [_vp, _i32, _fp, _fp, _fp, _vp, _vp, _vp, _fp, _fp, _i32, _i32,
-                                     _i32, _i64, _i64, _i64, _i64, _i64, _i64, _fp, _vp]),
-    "sc_lucy_scan_bwd": (_i32, [_vp, _i32, _fp, _fp, _vp, _fp, _vp, _fp, _fp, _fp, _i32, _i32, _i32,
-                               _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                               _vp]),
-    "sc_lucy_scan_fwd_ln": (_i32, [_vp, _i32, _fp, _fp, _fp, _vp, _vp, _vp, _fp, _fp, _i32, _i32,
-                                  _i32, _i64, _i64, _i64, _i64, _i64, _i64, _fp, _fp, _fp, _fp, _fp,
-                                  _c.c_float, _vp]),
-    "sc_lucy_scan_bwd_ln": (_i32, [_vp, _i32, _fp, _fp, _vp, _fp, _vp, _fp, _fp, _fp, _i32, _i32,
-                                  _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64, _i64,
-                                  _fp, _fp, _vp]),
-    "sc_ln_fold_prep": (_i32, [_vp, _i32, _vp]),
-    "sc_ln_fold_bwd": (_i32, [_vp, _vp, _i32, _fp, _vp, _i64, _i32, _vp]),
-    "sc_ln_fold_wgrad_workspace_numel": (_i64, [_i32, _i32]),
-    "sc_ln_fold_wgrad": (_i32, [_fp, _fp, _i64, _fp, _fp, _fp, _i32, _i32, _fp, _fp, _fp, _vp]),
-    "sc_decay_scan_fwd": (_i32, [_vp, _vp, _vp, _i32, _fp, _i32, _i32, _i32, _i64, _i64, _i64, _vp]),
-    "sc_decay_scan_bwd": (_i32, [_vp, _vp, _vp, _vp, _vp, _i32, _fp, _fp, _i32, _i32, _i32,
-                                _i64, _i64, _i64, _vp]),
-    "sc_layernorm_supported": (_i32, [_i32, _i32]),
-    "sc_layernorm_fwd": (_i32, [_vp, _i32, _fp, _fp, _vp, _fp, _fp, _i64, _i32, _c.c_float, _vp]),
-    "sc_layernorm_bwd_workspace_numel": (_i64, [_i64, _i32]),
-    "sc_layernorm_bwd": (_i32, [_vp, _vp, _i32, _fp, _fp, _fp, _vp, _fp, _fp, _i64, _i32, _vp]),
-    "sc_ctc_workspace_bytes": (_c.c_size_t, [_i32, _i32, _i32]),
-    "sc_ctc_fwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp,
-                         _i32, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_ctc_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _i32, _vp, _vp,
-                         _i32, _fp, _fp, _vp, _i32, _vp, _c.c_size_t, _vp]),
-    "sc_ctc_fwd_ex": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _i32, _vp,
-                            _vp, _i32, _fp, _i64, _i64, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_ctc_bwd_ex": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i64, _i32, _vp,
-                            _vp, _i32, _fp, _i64, _i64, _fp, _fp, _vp, _i32, _vp, _c.c_size_t,
-                            _vp]),
-    "sc_ctc_split_rows": (_i32, [_fp, _i64, _fp, _i32, _i32, _vp, _i64, _i32, _i32, _vp, _fp,
-                                 _i32, _vp]),
-    "sc_ctc_greedy_decode": (_i32, [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _i32, _vp, _vp, _vp]),
-    "sc_colsum_workspace_bytes": (_c.c_size_t, [_i64, _i64]),
-    "sc_colsum": (_i32, [_vp, _i32, _i64, _i64, _i64, _i64, _i64, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_fbank_frames": (_i64, [_i64]),
-    "sc_fbank_workspace_bytes": (_c.c_size_t, []),
-    "sc_fbank": (_i32, [_vp, _i32, _i64, _i64, _i32, _c.c_float, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_ctc_mean": (_i32, [_fp, _vp, _i32, _fp, _fp, _vp]),
-    "sc_ctc_greedy_step": (_i32, [_vp, _i32, _i32, _i32, _i64, _fp, _i32, _vp, _vp, _i64, _vp]),
-    "sc_lucy_step_supported": (_i32, [_i32, _i32]),
-    "sc_lucy_step_ln": (_i32, [_vp, _i32, _fp, _fp, _c.c_float, _vp, _i32, _i32, _vp]),
-    "sc_lucy_step_cell": (_i32, [_i32, _vp, _i32, _i64, _vp, _vp, _fp, _fp, _fp, _fp, _c.c_float,
-                                 _fp, _fp, _vp, _fp, _i32, _i32, _vp]),
-    "sc_lucy_frame_gemm": (_i32, [_i32, _fp, _i64, _i32, _fp, _fp, _vp, _i32, _c.c_float, _vp, _i32,
-                                  _i64, _fp, _i32, _i32, _fp, _i64, _vp, _fp, _vp, _fp, _fp, _vp]),
-    "sc_lucy_frame_cellb": (_i32, [_fp, _vp, _i32, _fp, _vp, _i32, _fp, _fp, _fp, _fp, _c.c_float,
-                                   _fp, _fp, _i64, _fp, _i32, _i32, _vp]),
-    "sc_lucy_frame_gemm_multi": (_i32, [_i32, _i32, _c.c_float, _vp, _i32, _vp]),
-    "sc_lucy_frame_cellb_multi": (_i32, [_c.c_float, _vp, _i32, _vp]),
-    "sc_lucy_tframe_layer": (_i32, [_fp, _i64, _i32, _fp, _fp, _vp, _i32, _c.c_float, _vp, _i32,
-                                    _i64, _fp, _i32, _i32, _fp, _fp, _fp, _i64, _vp, _fp, _vp]),
-    "sc_lucy_tframe_layer_multi": (_i32, [_i32, _c.c_float, _vp, _i32, _vp]),
-    "sc_ctc_greedy_frames": (_i32, [_vp, _i32, _i32, _i32, _i32, _i64, _i64, _fp, _i64, _i32, _vp,
-                                    _vp, _i64, _i64, _vp]),
-    "sc_mlstm_supported": (_i32, [_i32, _i32, _i32]),
-    "sc_mlstm_chunk_state_numel": (_i64, [_i32, _i32, _i32, _i32]),
-    "sc_mlstm_fwd": (_i32, [_vp, _vp, _vp, _i32, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32, _i32,
-                           _c.c_float, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
-    "sc_mlstm_bwd": (_i32, [_vp, _vp, _vp, _i32, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _fp, _fp, _fp,
-                           _fp, _i32, _i32, _i32, _i32, _c.c_float, _fp, _fp, _vp, _vp, _vp, _fp,
-                           _fp, _vp, _vp]),
-    "sc_mlstm_fwd_io": (_i32, [_vp, _vp, _vp, _i32, _i32, _fp, _fp, _fp, _fp, _fp, _i32, _i32, _i32,
-                              _i32, _c.c_float, _vp, _vp, _fp, _fp, _fp, _fp, _fp, _vp, _vp]),
-    "sc_mlstm_bwd_io": (_i32, [_vp, _vp, _vp, _i32, _i32, _fp, _fp, _vp, _vp, _fp, _fp, _vp, _fp, _fp,
-                              _fp, _fp, _i32, _i32, _i32, _i32, _c.c_float, _fp, _fp, _vp, _vp, _vp,
-                              _fp, _fp, _vp, _vp]),
-    "sc_mlstm_gate_bwd": (_i32, [_fp, _fp, _fp, _i32, _i32, _fp, _vp, _vp, _i32, _i64, _i32, _i32,
-                                _c.c_float, _vp]),
-    "sc_xlstm_part_rows": (_i32, [_i64]),
-    "sc_rmsnorm_fwd": (_i32, [_vp, _fp, _vp, _fp, _i64, _i32, _c.c_float, _vp]),
-    "sc_rmsnorm_bwd": (_i32, [_vp, _vp, _fp, _fp, _vp, _fp, _i64, _i32, _vp]),
-    "sc_rmsnorm_add_fwd": (_i32, [_vp, _vp, _vp, _fp, _vp, _fp, _i64, _i32, _c.c_float, _vp]),
-    "sc_rmsnorm_add_bwd": (_i32, [_vp, _vp, _vp, _fp, _fp, _vp, _fp, _i64, _i32, _vp]),
-    "sc_mhln_gate_fwd": (_i32, [_vp, _vp, _i64, _fp, _vp, _fp, _fp, _i32, _i32, _i32, _i32,
-                                _c.c_float, _vp]),
-    "sc_mhln_gate_bwd": (_i32, [_vp, _vp, _i64, _fp, _fp, _fp, _vp, _i64, _vp, _vp, _i64, _fp,
-                                _i32, _i32, _i32, _i32, _vp]),
-    "sc_mhln_gate_fwd_h16": (_i32, [_vp, _vp, _i64, _fp, _vp, _fp, _fp, _i32, _i32, _i32, _i32,
-                                _c.c_float, _vp]),
-    "sc_mhln_gate_bwd_h16": (_i32, [_vp, _vp, _i64, _fp, _fp, _fp, _vp, _i64, _vp, _vp, _i64, _fp,
-                                _i32, _i32, _i32, _i32, _vp]),
-    "sc_swiglu_fwd": (_i32, [_vp, _vp, _i64, _i32, _vp]),
-    "sc_swiglu_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _vp]),
-    "sc_adam_parts": (_i64, [_vp, _i32]),
-    "sc_adam_sumsq": (_i32, [_vp, _i32, _fp, _vp]),
-    "sc_adam_step": (_i32, [_vp, _i32, _fp, _i64, _c.c_double, _c.c_double, _c.c_double,
-                           _c.c_double, _c.c_double, _c.c_double, _i32, _c.c_double, _c.c_double,
-                           _fp, _vp]),
-    "sc_weight_images": (_i32, [_vp, _i32, _vp]),
-    "sc_rnnt_workspace_bytes": (_c.c_size_t, [_i32, _i32, _i32]),
-    "sc_rnnt_joint_geometry": (_i32, [_i32, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "sc_rnnt_joint_fwd": (_i32, [_fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
-                                 _vp, _i32, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_rnnt_joint_bwd": (_i32, [_fp, _fp, _vp, _fp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp,
-                                 _vp, _i32, _fp, _fp, _fp, _fp, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_rnnt_fwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i64,
-                          _vp, _vp, _i32, _fp, _vp, _c.c_size_t, _vp]),
-    "sc_rnnt_bwd": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _i64, _vp, _vp, _i64,
-                          _vp, _vp, _i32, _fp, _vp, _i32, _vp, _c.c_size_t, _vp]),
-    "sc_rnnt_greedy_decode": (_i32, [_vp, _vp, _vp, _i32, _fp, _i32, _i32, _i32, _i32, _i64, _i64,
-                                     _vp, _fp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _i32, _vp,
-                                     _vp]),
-    "sc_ctc_beam_state_bytes": (_c.c_size_t, [_i32, _i32, _i32]),
-    "sc_ctc_beam_workspace_bytes": (_c.c_size_t, [_i32, _i32, _i32]),
-    "sc_ctc_beam_reset": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _fp, _vp]),
-    "sc_ctc_beam_frames": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _i64, _i64, _vp, _fp, _i64,
-                                  _i64, _i32, _i32, _i32, _vp, _c.c_size_t, _vp, _c.c_size_t,
-                                  _vp]),
-    "sc_ctc_beam_result": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _vp, _i32, _vp, _fp, _vp,
-                                  _vp]),
-    "sc_rnnt_beam_state_bytes": (_c.c_size_t, [_i32, _i32, _i32, _i32]),
-    "sc_rnnt_beam_workspace_bytes": (_c.c_size_t, [_i32, _i32]),
-    "sc_rnnt_beam_reset": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _i32, _fp, _vp]),
-    "sc_rnnt_beam_frames": (_i32, [_vp, _vp, _vp, _i32, _fp, _i32, _i32, _i32, _i32, _i64, _i64,
-                                   _vp, _fp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _c.c_size_t,
-                                   _vp, _c.c_size_t, _vp]),
-    "sc_rnnt_beam_result": (_i32, [_vp, _c.c_size_t, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp,
-                                   _fp, _vp, _vp]),
-}
+def _declare(text, structs, where):
+    """`[const] type a, *b` -> [(name, ctype), ...].  Pointers stay untyped: callers pass None, raw
+    integer addresses, c_void_p and ctypes arrays."""
+    m = re.fullmatch(r"\s*(?:const\s+)?(?:struct\s+)?(\w+)\b(.*)", text, re.S)
+    out = []
+    for d in m.group(2).split(",") if m else [""]:
+        dm = re.fullmatch(r"\s*(\**)\s*(\w*)\s*", d) if m else None
+        if not dm or dm.group(2) in ("const", "struct"):
+            raise ValueError(f"statecatcher.h: cannot parse {text.strip()!r} in: {where}")
+        base, stars, name = m.group(1), dm.group(1), dm.group(2)
+        if base not in ((_POINTEES | set(structs)) if stars else _SCALARS):
+            raise ValueError(f"statecatcher.h: type of {text.strip()!r} not supported in: {where}")
+        out.append((name, ctypes.c_void_p if stars else _SCALARS[base]))
+    return out
+
+
+def parse_header(text):
+    """Header text -> (constants {name: int}, structs {name: ctypes.Structure class}, signatures
+    {name: (restype, argtypes)}).  Fails closed: a declaration it does not fully understand raises
+    ValueError quoting it; nothing is skipped or guessed."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    consts = {}
+    for name, value in _DEFINE.findall(text):
+        m = _INTEGER.fullmatch(value)
+        if not m:
+            raise ValueError(f"statecatcher.h: #define {name}{value} is no integer constant")
+        consts[name] = int(m.group(1) or m.group(2))
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text, wrapped = re.subn(r'extern\s+"C"\s*\{', "", text.rstrip(), count=1)
+    if wrapped:
+        if not text.endswith("}"):
+            raise ValueError('statecatcher.h: extern "C" { is never closed')
+        text = text[:-1]
+    structs, sigs, pos = {}, {}, 0
+    while True:
+        pos = _SPACE.match(text, pos).end()
+        if pos == len(text):
+            return consts, structs, sigs
+        m = _STRUCT.match(text, pos) or _PROTO.match(text, pos)
+        where = " ".join((m.group(0) if m else text[pos:].partition(";")[0]).split())
+        if not m:
+            raise ValueError(f"statecatcher.h: cannot parse declaration: {where}")
+        if m.re is _STRUCT:
+            tag, body, name = m.groups()
+            fields = [f for part in body.split(";") if part.strip()
+                      for f in _declare(part, structs, where)]
+            if tag not in ("", name) or not fields or not all(n for n, _ in fields):
+                raise ValueError(f"statecatcher.h: cannot parse struct: {where}")
+            structs[name] = type(name, (ctypes.Structure,), {
+                "_fields_": fields, "__doc__": f"{name} (include/statecatcher.h)."})
+        else:
+            ret, name, params = m.groups()
+            ret = " ".join(ret.replace("*", " * ").split())
+            if ret not in _RETURNS:
+                raise ValueError(f"statecatcher.h: return type {ret!r} not supported in: {where}")
+            params = [] if params.strip() in ("", "void") else params.split(",")
+            sigs[name] = (_RETURNS[ret], [_declare(p, structs, where)[0][1] for p in params])
+        pos = m.end()
+
+
+def _read_header():
+    try:
+        with open(HEADER_PATH) as f:
+            return f.read()
+    except OSError as e:
+        raise RuntimeError(f"statecatcher C ABI header missing: {HEADER_PATH} (the Python binding "
+                           f"is derived from it): {e}") from None
+
+
+CONSTANTS, STRUCTS, _SIGS = parse_header(_read_header())
+globals().update(CONSTANTS)   # SC_EINVAL, SC_F32, SC_MAX_FRAME_JOBS, SC_FRAME_PLAIN, ...
 EXPORTED = tuple(_SIGS)
-
-
-class AdamTensor(ctypes.Structure):
-    """sc_adam_tensor (include/statecatcher.h)."""
-    _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("n", _i64)]
-
-
-class ImageJob(ctypes.Structure):
-    """sc_image_job (include/statecatcher.h)."""
-    _fields_ = [("src", _vp), ("dst", _vp), ("dst_t", _vp), ("rows", _i64), ("cols", _i64),
-                ("cols_pad", _i64), ("ld_src", _i64), ("block_d", _i64), ("col_scale", _vp),
-                ("row_shift", _vp)]
-
-
-class LnFoldJob(ctypes.Structure):
-    """sc_ln_fold_job (include/statecatcher.h)."""
-    _fields_ = [("w", _vp), ("gamma", _vp), ("beta", _vp), ("bias", _vp), ("shift", _vp),
-                ("bias_out", _vp), ("rowsum", _vp), ("ld", _i64), ("rows", _i64), ("D", _i64)]
-
-
-class FrameGemmJob(ctypes.Structure):
-    """sc_frame_gemm_job (include/statecatcher.h)."""
-    _fields_ = [("x", _vp), ("ldx", _i64), ("K", _i32), ("ln_w", _vp), ("ln_b", _vp),
-                ("st_in", _vp), ("nst_in", _i32), ("w", _vp), ("ldw", _i64), ("bias", _vp),
-                ("B", _i32), ("N", _i32), ("y", _vp), ("ldy", _i64), ("st_out", _vp), ("z", _vp),
-                ("st_z", _vp), ("s", _vp), ("mask", _vp)]
-
-
-class FrameCellJob(ctypes.Structure):
-    """sc_frame_cell_job (include/statecatcher.h)."""
-    _fields_ = [("z", _vp), ("st_z", _vp), ("nst_z", _i32), ("hp", _vp), ("st_h", _vp),
-                ("nst_h", _i32), ("lnz_w", _vp), ("lnz_b", _vp), ("lnh_w", _vp), ("lnh_b", _vp),
-                ("h", _vp), ("out", _vp), ("ldo", _i64), ("mask", _vp), ("B", _i32), ("D", _i32)]
-
-
-class TFrameJob(ctypes.Structure):
-    """sc_tframe_job (include/statecatcher.h)."""
-    _fields_ = [("x", _vp), ("ldx", _i64), ("K", _i32), ("ln_w", _vp), ("ln_b", _vp),
-                ("st_in", _vp), ("nst_in", _i32), ("w", _vp), ("ldw", _i64), ("bias", _vp),
-                ("B", _i32), ("D", _i32), ("h", _vp), ("s", _vp), ("out", _vp), ("ldo", _i64),
-                ("st_out", _vp), ("mask", _vp)]
-
+ABI_VERSION = CONSTANTS["SC_ABI_VERSION"]   # load() refuses a library built from another header
+_DTYPE = {torch.float32: CONSTANTS["SC_F32"], torch.bfloat16: CONSTANTS["SC_BF16"],
+          torch.float16: CONSTANTS["SC_F16"]}
+AdamTensor = STRUCTS["sc_adam_tensor"]
+ImageJob = STRUCTS["sc_image_job"]
+LnFoldJob = STRUCTS["sc_ln_fold_job"]
+FrameGemmJob = STRUCTS["sc_frame_gemm_job"]
+FrameCellJob = STRUCTS["sc_frame_cell_job"]
+TFrameJob = STRUCTS["sc_tframe_job"]
 
 _LIB = None
 

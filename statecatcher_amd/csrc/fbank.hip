@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(256) fbank_kernel(FbankArgs a) {
     const float mmax = hz_to_mel(0.5f * a.sr);
     fpts[tid] = mel_to_hz(mmax * (float)tid / (float)(kMels + 1));
   }
-  if (a.kind == 0) {
+  if (a.kind == SC_FBANK_MFCC) {
     const float s0 = sqrtf(1.0f / kMels), s1 = sqrtf(2.0f / kMels);
     for (int i = tid; i < kMels * kMels; i += 256) {
       const int m = i / kMels, c = i % kMels;
@@ -140,7 +140,7 @@ __global__ void __launch_bounds__(256) fbank_kernel(FbankArgs a) {
         const float wk = fmaxf(0.0f, fminf((fk - f0) * i01, (f2 - fk) * i12));
         acc = fmaf(wk, p[k], acc);
       }
-      if (a.kind == 0) {
+      if (a.kind == SC_FBANK_MFCC) {
         l[m] = logf(acc + 1e-6f);
       } else {
         const float db = 10.0f * log10f(fmaxf(acc, 1e-10f));
@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(256) fbank_kernel(FbankArgs a) {
         runmax = fmaxf(runmax, db);
       }
     }
-    if (a.kind == 0) {
+    if (a.kind == SC_FBANK_MFCC) {
       wave_lds_sync();
       for (int c = lane; c < kMels; c += 64) {
         float acc = 0.0f;
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(256) fbank_kernel(FbankArgs a) {
     }
     wave_lds_sync();   // the wave's scratch is reused by its next frame
   }
-  if (a.kind == 1) {
+  if (a.kind == SC_FBANK_MEL) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) runmax = fmaxf(runmax, __shfl_xor(runmax, o));
     if (lane == 0 && runmax > -__builtin_huge_valf()) atomicMax(a.dbmax, order_key(runmax));
@@ -187,21 +187,23 @@ extern "C" int sc_fbank(const float* audio, int B, int64_t n_samples, int64_t au
                         int kind, float sample_rate, float* out, void* workspace,
                         size_t workspace_bytes, void* stream) {
   clear_error();
-  SC_REQUIRE(kind == 0 || kind == 1, "sc_fbank: kind must be 0 (mfcc) or 1 (mel), got %d", kind);
+  SC_REQUIRE(kind == SC_FBANK_MFCC || kind == SC_FBANK_MEL,
+             "sc_fbank: kind must be 0 (mfcc) or 1 (mel), got %d", kind);
   SC_REQUIRE(B >= 0 && n_samples >= 0 && sample_rate > 0.0f, "sc_fbank: bad shape / rate");
   const int64_t F = sc_fbank_frames(n_samples);
   if (B == 0 || F == 0) return 0;
   SC_REQUIRE(audio && out, "sc_fbank: null pointer");
   SC_REQUIRE(audio_stride >= n_samples, "sc_fbank: row stride %lld < samples %lld",
              (long long)audio_stride, (long long)n_samples);
-  SC_REQUIRE(kind == 0 || (workspace && workspace_bytes >= 4), "sc_fbank: mel needs the workspace");
+  SC_REQUIRE(kind == SC_FBANK_MFCC || (workspace && workspace_bytes >= 4),
+             "sc_fbank: mel needs the workspace");
   hipStream_t st = (hipStream_t)stream;
   FbankArgs a{audio, B, n_samples, audio_stride, F, kind, sample_rate, out, (unsigned*)workspace};
-  if (kind == 1) zero_async(workspace, 4, st);
+  if (kind == SC_FBANK_MEL) zero_async(workspace, 4, st);
   const int64_t frames = (int64_t)B * F;
   const unsigned grid = (unsigned)std::min<int64_t>((frames + 3) / 4, 2048);
   hipLaunchKernelGGL(fbank_kernel, dim3(grid), dim3(256), 0, st, a);
-  if (kind == 1) {
+  if (kind == SC_FBANK_MEL) {
     const int64_t n = frames * kMels;
     hipLaunchKernelGGL(fbank_topdb_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 4096)),
                        dim3(256), 0, st, out, n, (const unsigned*)workspace);

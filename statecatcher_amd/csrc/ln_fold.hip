@@ -32,7 +32,7 @@ struct FoldPrepJob {
   int64_t ld;
   int rows, D;
 };
-constexpr int kMaxFoldJobs = 16;
+constexpr int kMaxFoldJobs = SC_MAX_FOLD_JOBS;
 struct FoldPrepTable {
   FoldPrepJob j[kMaxFoldJobs];
   int32_t first[kMaxFoldJobs + 1];   // prefix of the jobs' workgroups (4 rows each)

@@ -39,8 +39,8 @@
 
 namespace sc {
 
-enum { FR_PLAIN = 0, FR_STATS = 1, FR_CELL_UNFUSED = 2, FR_CELL_FUSED = 3,
-       FR_CELL_T = 4 };   // (4: the LucyRNNtriton layer, sc_lucy_tframe_layer only)
+enum { FR_PLAIN = SC_FRAME_PLAIN, FR_STATS = SC_FRAME_STATS, FR_CELL_UNFUSED = SC_FRAME_CELL_UNFUSED,
+       FR_CELL_FUSED = SC_FRAME_CELL_FUSED, FR_CELL_T = 4 };   // (4: the LucyRNNtriton layer, sc_lucy_tframe_layer only)
 constexpr bool is_cell(int epi) { return epi >= FR_CELL_UNFUSED; }
 
 struct FrameGemmArgs {
@@ -459,7 +459,7 @@ __global__ void __launch_bounds__(64 * NT * KS, 4) lucy_frame_gemm(FrameGemmArgs
 // the layers of a frame block run as a wavefront over (frame, layer), so the jobs of a launch are
 // different layers at different frames (streaming.py).  Workgroups past a job's column or row
 // blocks leave at once (uniformly, before any barrier).
-constexpr int kMaxFrameJobs = 8;
+constexpr int kMaxFrameJobs = SC_MAX_FRAME_JOBS;
 struct FrameGemmJobs {
   FrameGemmArgs j[kMaxFrameJobs];
 };

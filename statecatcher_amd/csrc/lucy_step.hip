@@ -20,7 +20,8 @@
 
 namespace sc {
 
-enum { MODE_FUSED = 0, MODE_UNFUSED_A = 1, MODE_UNFUSED_B = 2 };
+enum { MODE_FUSED = SC_STEP_FUSED, MODE_UNFUSED_A = SC_STEP_UNFUSED_A,
+       MODE_UNFUSED_B = SC_STEP_UNFUSED_B };
 
 struct StepArgs {
   const void* g;   // gate GEMM output rows (dtype DT), row stride g_stride

@@ -161,7 +161,7 @@ __global__ void __launch_bounds__(kThreads) adam_step_kernel(AdamTable t, StepSc
 }
 
 // ------------------------------------------------------------------------ weight images ----
-constexpr int kMaxJobs = 16;
+constexpr int kMaxJobs = SC_MAX_IMAGE_JOBS;
 constexpr int kTile = 64;
 
 struct ImageTable {

@@ -366,14 +366,19 @@ def weight_images(specs):
     return out
 
 
+def _launch_jobs(name, job_type, cap, jobs, stream, *scalars):
+    """lib.<name>(*scalars, jobs, njobs, stream) over a list of job_type structs, in launches of at
+    most cap jobs (the header's per-call limit for that entry point); no jobs, no launch."""
+    fn = getattr(_lib.load(), name)
+    for k in range(0, len(jobs), cap):
+        part = jobs[k:k + cap]
+        check(fn(*scalars, (job_type * len(part))(*part), len(part), stream), name)
+
+
 def _image_jobs(jobs, keep):
     require_device(*keep)
-    lib = _lib.load()
-    for k in range(0, len(jobs), 16):
-        part = jobs[k:k + 16]
-        rc = lib.sc_weight_images((_lib.ImageJob * len(part))(*part), len(part),
-                                  stream_of(keep[0]))
-        check(rc, "sc_weight_images")
+    _launch_jobs("sc_weight_images", _lib.ImageJob, _lib.SC_MAX_IMAGE_JOBS, jobs,
+                 stream_of(keep[0]))
 
 
 def cast_pad_bf16(x, kp):
@@ -599,11 +604,8 @@ def fold_images(specs):
         _FOLD[w] = (key, out[i])
     if preps:
         require_device(*keep)
-        lib = _lib.load()
-        for k in range(0, len(preps), 16):
-            part = preps[k:k + 16]
-            check(lib.sc_ln_fold_prep((_lib.LnFoldJob * len(part))(*part), len(part),
-                                      stream_of(keep[0])), "sc_ln_fold_prep")
+        _launch_jobs("sc_ln_fold_prep", _lib.LnFoldJob, _lib.SC_MAX_FOLD_JOBS, preps,
+                     stream_of(keep[0]))
         _image_jobs(jobs, keep)
         for o in out:   # (new entries) r permuted to the image's row order, after the prep
             if o is not None and o[4] is not o[3]:
@@ -1143,7 +1145,8 @@ def ctc_greedy_step(logits, prev, emit, mask=None, blank=0):
 
 
 # ------------------------------------------------------------------- streaming LucyRNN step --
-STEP_FUSED, STEP_UNFUSED_A, STEP_UNFUSED_B = 0, 1, 2
+STEP_FUSED, STEP_UNFUSED_A, STEP_UNFUSED_B = (_lib.SC_STEP_FUSED, _lib.SC_STEP_UNFUSED_A,
+                                              _lib.SC_STEP_UNFUSED_B)
 
 
 def lucy_step_ln(x, w, b, out, eps=1e-5):
@@ -1167,7 +1170,8 @@ def lucy_step_cell(mode, g, h, s, out, lnz=None, lnh=None, u=None, hp=None, mask
     check(rc, "sc_lucy_step_cell")
 
 
-FRAME_PLAIN, FRAME_STATS, FRAME_CELL_UNFUSED, FRAME_CELL_FUSED = 0, 1, 2, 3
+FRAME_PLAIN, FRAME_STATS, FRAME_CELL_UNFUSED, FRAME_CELL_FUSED = (
+    _lib.SC_FRAME_PLAIN, _lib.SC_FRAME_STATS, _lib.SC_FRAME_CELL_UNFUSED, _lib.SC_FRAME_CELL_FUSED)
 
 
 def lucy_frame_gemm(epi, x, w, bias, y, st_out=None, ln=None, st_in=None, z=None, st_z=None,
@@ -1212,16 +1216,11 @@ def frame_gemm_job(x, w, bias, y, st_out=None, ln=None, st_in=None, z=None, st_z
 
 
 def lucy_frame_gemm_multi(epi, w_dtype, jobs, stream, eps=1e-5):
-    """Independent frame GEMMs of one epilogue kind (FrameGemmJob list, <= 8 per launch: longer
-    lists take ceil(n / 8) launches) -- sc_lucy_frame_gemm_multi.  w_dtype: torch dtype of
-    every job's weights.  No allocation: safe inside a hipGraph capture."""
-    lib = _lib.load()
-    code = dtype_code(torch.empty(0, dtype=w_dtype))
-    for k in range(0, len(jobs), 8):
-        part = jobs[k:k + 8]
-        check(lib.sc_lucy_frame_gemm_multi(int(epi), code, float(eps),
-                                           (_lib.FrameGemmJob * len(part))(*part), len(part),
-                                           stream), "sc_lucy_frame_gemm_multi")
+    """Independent frame GEMMs of one epilogue kind (FrameGemmJob list, <= SC_MAX_FRAME_JOBS per
+    launch: longer lists take several launches) -- sc_lucy_frame_gemm_multi.  w_dtype: torch dtype
+    of every job's weights.  No allocation: safe inside a hipGraph capture."""
+    _launch_jobs("sc_lucy_frame_gemm_multi", _lib.FrameGemmJob, _lib.SC_MAX_FRAME_JOBS, jobs, stream,
+                 int(epi), dtype_code(torch.empty(0, dtype=w_dtype)), float(eps))
 
 
 def frame_cell_job(z, hp, h, out, st_z=None, st_h=None, lnz=None, lnh=None, mask=None):
@@ -1235,12 +1234,10 @@ def frame_cell_job(z, hp, h, out, st_z=None, st_h=None, lnz=None, lnh=None, mask
 
 
 def lucy_frame_cellb_multi(jobs, stream, eps=1e-5):
-    """Independent lucy_frame_cellb calls in <= 8-job launches (sc_lucy_frame_cellb_multi)."""
-    lib = _lib.load()
-    for k in range(0, len(jobs), 8):
-        part = jobs[k:k + 8]
-        check(lib.sc_lucy_frame_cellb_multi(float(eps), (_lib.FrameCellJob * len(part))(*part),
-                                            len(part), stream), "sc_lucy_frame_cellb_multi")
+    """Independent lucy_frame_cellb calls in launches of <= SC_MAX_FRAME_JOBS jobs
+    (sc_lucy_frame_cellb_multi)."""
+    _launch_jobs("sc_lucy_frame_cellb_multi", _lib.FrameCellJob, _lib.SC_MAX_FRAME_JOBS, jobs,
+                 stream, float(eps))
 
 
 def lucy_tframe_layer(x, w, bias, h, s, out, st_out=None, ln=None, st_in=None, mask=None,
@@ -1272,15 +1269,12 @@ def tframe_job(x, w, bias, h, s, out, st_out=None, ln=None, st_in=None, mask=Non
 
 
 def lucy_tframe_layer_multi(w_dtype, jobs, stream, eps=1e-5):
-    """Independent LucyRNNtriton layer frames (TFrameJob list, <= 8 per launch: longer lists take
-    ceil(n / 8) launches) -- sc_lucy_tframe_layer_multi.  The jobs of a launch run concurrently:
-    none may read what another writes.  No allocation: safe inside a hipGraph capture."""
-    lib = _lib.load()
-    code = dtype_code(torch.empty(0, dtype=w_dtype))
-    for k in range(0, len(jobs), 8):
-        part = jobs[k:k + 8]
-        check(lib.sc_lucy_tframe_layer_multi(code, float(eps), (_lib.TFrameJob * len(part))(*part),
-                                             len(part), stream), "sc_lucy_tframe_layer_multi")
+    """Independent LucyRNNtriton layer frames (TFrameJob list, <= SC_MAX_FRAME_JOBS per launch:
+    longer lists take several launches) -- sc_lucy_tframe_layer_multi.  The jobs of a launch run
+    concurrently: none may read what another writes.  No allocation: safe inside a hipGraph
+    capture."""
+    _launch_jobs("sc_lucy_tframe_layer_multi", _lib.TFrameJob, _lib.SC_MAX_FRAME_JOBS, jobs, stream,
+                 dtype_code(torch.empty(0, dtype=w_dtype)), float(eps))
 
 
 def ctc_greedy_frames(logits, prev, emit, mask=None, blank=0):
@@ -1648,7 +1642,7 @@ def fbank(audio, kind="mfcc", sample_rate=16000):
     require_device(audio)
     if audio.dim() != 2:
         raise ValueError(f"fbank: audio must be [B, N], got {tuple(audio.shape)}")
-    codes = {"mfcc": 0, "mel": 1}
+    codes = {"mfcc": _lib.SC_FBANK_MFCC, "mel": _lib.SC_FBANK_MEL}
     if kind not in codes:
         raise ValueError(f"Unsupported frontend: {kind}")
     a = audio.to(torch.float32)

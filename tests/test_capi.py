@@ -30,6 +30,15 @@ def test_library_exports_every_header_symbol(lib):
         assert hasattr(lib, n), n
 
 
+def test_library_exports_every_bound_symbol(lib):
+    """The reverse: every name the binding derives from the header resolves in the library."""
+    from statecatcher_amd import _lib
+    handle = ctypes.CDLL(_lib.LIB_PATH)   # a fresh handle: nothing load() attached counts
+    assert len(_lib.EXPORTED) >= 12
+    for n in _lib.EXPORTED:
+        assert hasattr(handle, n), n
+
+
 def test_binding_covers_header(lib):
     from statecatcher_amd import _lib
     assert sorted(_lib.EXPORTED) == header_functions()
