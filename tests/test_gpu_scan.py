@@ -4,13 +4,16 @@ the oracle.  Tolerances:
   bf16 gates: compared with the oracle fed the SAME bf16-rounded gates; outputs are stored in
               bf16 so the bound is 1e-2 rel + 1e-2 abs (2.5 bf16 ulps);
   gradients: 1e-3 relative to the largest |grad| of the tensor (mixed abs/rel; the per-element
-              normaliser x/sqrt(x^2+1e-6) has derivatives up to ~1e3 near 0).
+              normaliser x/sqrt(x^2+1e-6) has derivatives up to ~1e3 near 0) -- a bound
+              that one outlier of the k / v planes sets, so every gradient and s_last is ALSO
+              checked elementwise at the scale of its own step (tests/scan_cases.py).
 """
 import numpy as np
 import pytest
 import torch
 
 from oracle import lucy_scan as oscan
+from tests import scan_cases
 from tests.conftest import cases, load_golden
 
 pytestmark = pytest.mark.gpu
@@ -70,6 +73,7 @@ def test_fwd_shapes_vs_oracle(B, T, D):
     ro, rs = oscan.lucy_scan_fwd(gates, h0, s0)
     np.testing.assert_allclose(out, ro, rtol=1e-3, atol=2e-5)
     np.testing.assert_allclose(s, rs, rtol=1e-3, atol=1e-4 * max(1.0, np.abs(rs).max()))
+    scan_cases.assert_s_last(gates, h0, s0, s)
 
 
 def test_T0_returns_initial_state():
@@ -91,6 +95,7 @@ def test_fwd_half_gates_vs_oracle_on_rounded_inputs(dtype):
     ro, rs = oscan.lucy_scan_fwd(gates.float().numpy(), h0, s0)
     np.testing.assert_allclose(out, ro, rtol=1e-2, atol=1e-2)
     np.testing.assert_allclose(s, rs, rtol=1e-3, atol=1e-4 * max(1.0, np.abs(rs).max()))
+    scan_cases.assert_s_last(gates.float().numpy(), h0, s0, s)
 
 
 @pytest.mark.parametrize("name", cases(load_golden("scan_bwd"), "dgates"))
@@ -107,6 +112,13 @@ def test_bwd_fp32_vs_autograd_fixture(name):
     for got, key in [(g.grad, "/dgates"), (h0.grad, "/dh0"), (s0.grad, "/ds0")]:
         ref = zb[name + key]
         np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=1e-3, atol=1e-3 * np.abs(ref).max())
+    # elementwise, against the fp64 oracle on the fixture's inputs (test_oracle_golden pins the
+    # oracle to these autograd fixtures)
+    case = scan_cases.make_case(zf[name + "/gates"], zf[name + "/h0"], zf[name + "/s0"],
+                                zb[name + "/dout"], zb[name + "/ds_last"])
+    scan_cases.assert_parity(case, {"dgates": g.grad.cpu().numpy(), "dh0": h0.grad.cpu().numpy(),
+                                    "ds0": s0.grad.cpu().numpy(), "out": out.detach().cpu().numpy(),
+                                    "s_last": s_last.detach().cpu().numpy()}, label=name)
 
 
 @pytest.mark.parametrize("B,T,D", [(2, 1, 16), (2, 64, 64), (3, 65, 100), (2, 300, 64), (4, 1500, 128)])
@@ -125,6 +137,10 @@ def test_bwd_shapes_vs_oracle(B, T, D):
     rg, rh, rs = oscan.lucy_scan_bwd(gates, h0, s0, dout, ds)
     for got, ref in [(g.grad, rg), (hh.grad, rh), (ss.grad, rs)]:
         np.testing.assert_allclose(got.cpu().numpy(), ref, rtol=1e-3, atol=1e-3 * np.abs(ref).max())
+    case = scan_cases.make_case(gates, h0, s0, dout, ds)
+    scan_cases.assert_parity(case, {"dgates": g.grad.cpu().numpy(), "dh0": hh.grad.cpu().numpy(),
+                                    "ds0": ss.grad.cpu().numpy(), "out": out.detach().cpu().numpy(),
+                                    "s_last": s_last.detach().cpu().numpy()}, label=f"{B}x{T}x{D}")
 
 
 def test_bwd_bf16_vs_oracle_on_rounded_inputs():
@@ -141,6 +157,10 @@ def test_bwd_bf16_vs_oracle_on_rounded_inputs():
     got = g.grad.float().cpu().numpy()
     # bf16-stored gradients: relative to the tensor's scale
     np.testing.assert_allclose(got, rg, rtol=2e-2, atol=1e-2 * np.abs(rg).max())
+    case = scan_cases.make_case(gates.float().numpy(), np.zeros((B, D)), np.zeros((B, D)),
+                                dout.float().numpy(), np.zeros((B, D)), "bf16")
+    scan_cases.assert_parity(case, {"dgates": got, "out": out.detach().float().cpu().numpy()},
+                             label="bf16 200x64")
 
 
 def test_full_size_bf16_determinism_and_segment_consistency():
@@ -278,8 +298,16 @@ def test_narrow_piece_path_vs_oracle(dtype, D, offset):
     tol = 1e-3 if dtype == torch.float32 else 1e-2
     np.testing.assert_allclose(out.float().cpu().numpy(), ro, rtol=tol, atol=tol)
     np.testing.assert_allclose(s.cpu().numpy(), rs, rtol=1e-3, atol=1e-4 * max(1.0, np.abs(rs).max()))
-    dg, _, _, _ = ops()._scan_bwd(gg, ck, torch.as_tensor(dout).to(dtype).to(DEV), None, False)
+    dg, dh0g, ds0g, _ = ops()._scan_bwd(gg, ck, torch.as_tensor(dout).to(dtype).to(DEV), None, False)
     rg, _, _ = oscan.lucy_scan_bwd(gr, h0, s0, torch.as_tensor(dout).to(dtype).float().numpy(),
                                    np.zeros((B, D)))
     np.testing.assert_allclose(dg.float().cpu().numpy(), rg, rtol=2 * tol,
                                atol=tol * np.abs(rg).max())
+    name = {torch.float32: "f32", torch.bfloat16: "bf16", torch.float16: "f16"}[dtype]
+    case = scan_cases.make_case(gr, h0, s0, torch.as_tensor(dout).to(dtype).float().numpy(),
+                                np.zeros((B, D)), name)
+    if name == "f16":
+        scan_cases.assert_fits_f16(scan_cases.reference(case))
+    scan_cases.assert_parity(case, {"dgates": dg.float().cpu().numpy(), "dh0": dh0g.cpu().numpy(),
+                                    "ds0": ds0g.cpu().numpy(), "out": out.float().cpu().numpy(),
+                                    "s_last": s.cpu().numpy()}, label=f"narrow {name} D={D}")
