@@ -40,6 +40,8 @@
  *                        of RNNTPredictorJoiner (model.py:112-145), offline and streaming
  *   sc_rnnt_beam_*    <- (absent in the reference) transducer beam search of the same joiner,
  *                        n-best with scores, offline and chunked
+ *   sc_ctc_align      <- (absent in the reference; its README plans hallucination filtering) CTC
+ *                        forced alignment: Viterbi path, token spans, per-frame / per-token scores
  */
 #ifndef STATECATCHER_H
 #define STATECATCHER_H
@@ -991,6 +993,64 @@ int sc_ctc_beam_frames(const void* x, int dtype, int is_logits, int B, int T, in
 int sc_ctc_beam_result(const void* state, size_t state_bytes, int B, int beam, int nbest,
                        int32_t* tokens, int cap, int32_t* lens, float* scores, int32_t* status,
                        void* stream);
+
+/*
+ * CTC forced alignment (csrc/ctc_align.hip): the best (Viterbi) alignment of a transcript to the
+ * frames, where each token lies, and how well it fits -- per frame, per token and in total.  The
+ * reference lists "on-the-fly hallucination detection & filtering" of its subtitle-cut segments as
+ * planned; a hallucinated or shifted transcript aligns badly.  sc_ctc_fwd gives one number per
+ * sequence; the transducer decoders return the frame of every token; this is the CTC counterpart.
+ *
+ * Inputs are those of sc_ctc_fwd: x [B][T][V] (fp32 / bf16 / f16, widened exactly on load; element
+ * strides stride_b, stride_t, inner 1), is_logits, targets int64 [B][max_target_len] (row stride
+ * target_stride), in_lens / tgt_lens int64 [B] (clamped into [0, T] / [0, max_target_len]), blank.
+ * max_target_len <= 1007.  A label outside [0, V) reads the nearest column, and a label equal to
+ * blank is never skipped into, both as in sc_ctc_fwd.
+ *
+ * Per sequence (T_b = in_lens[b], U = tgt_lens[b]) the blank-extended states are s = 0 .. 2U,
+ * ext[s] = blank for even s and targets[(s - 1) / 2] for odd s.
+ *   lp[t][v] = x[v] - logsumexp_v x (is_logits = 1) or x[v] (is_logits = 0); natural log, fp32
+ *   v[0][0] = lp[0][blank], v[0][1] = lp[0][ext[1]], every other state -inf
+ *   v[t][s] = lp[t][ext[s]] + max(v[t-1][s], v[t-1][s-1], v[t-1][s-2]), the s-2 term only for odd
+ *             s >= 3 with ext[s] != ext[s-2]; ties go to the smaller move (stay, step, skip)
+ *   the path ends in state 2U or 2U-1, whichever has the larger v[T_b-1] (a tie goes to 2U; U = 0
+ *   ends in state 0), and is followed back through the recorded moves.
+ * Arithmetic: each frame's emissions are shifted by c_t, the largest lp of that frame among the
+ * sequence's states (every path takes one emission per frame, so the path does not depend on it),
+ * v is re-centred on its maximum every 16 frames, and the sum of shifts and maxima is carried in
+ * fp64: an unshifted fp32 lattice at T = 1500 holds values near 1e4, whose rounding decides close
+ * moves.  This is what sc_ctc_fwd does for the loss.  An emission below -1e30 (or NaN) counts as
+ * impossible.  logsumexp is summed in pieces of 8 consecutive elements, piece c by lane c % 64,
+ * whatever the element type and the row's alignment: a 16-bit tensor aligns bit for bit as the
+ * fp32 tensor of the same values.  -inf logits (masked tokens) add exp = 0 to it.
+ *
+ * Outputs:
+ *   states   int32 [B][T]    the path's state at each frame t < T_b; -1 at t >= T_b
+ *   frame_lp fp32 [B][T]     lp[t][ext[states[t]]] (unshifted); 0 at t >= T_b
+ *   spans    int32 [B][max_target_len][2]  first frame and one past the last frame of the run of
+ *                            state 2u + 1; -1, -1 for u >= U
+ *   token_lp fp32 [B][max_target_len]  mean of frame_lp over the span, summed in frame order in
+ *                            fp32; 0 for u >= U
+ *   score    fp32 [B]        the path's total log-probability: fp64 (shifts + maxima) + the final
+ *                            value, rounded once
+ * A sequence with no valid alignment (T_b < U + the number of adjacent equal labels, or T_b = 0 <
+ * U) gets score -inf, states -1, spans -1 and zeros elsewhere; T_b = 0 with U = 0 gives score 0.
+ * A NaN in a sequence's rows makes that sequence's result unspecified; the call still completes
+ * with every index in range and the other sequences untouched.  B == 0 launches nothing.  Bad
+ * arguments return SC_EINVAL with sc_last_error set.
+ *
+ * workspace: at least sc_ctc_align_workspace_bytes(B, T, max_target_len) bytes, 16-byte aligned
+ * (the compact emission rows, the rows' normalisers and shifts, and 2 bits per state and frame of
+ * recorded moves); the size function returns 0 for arguments outside the limits.  No host sync, no
+ * allocation, no atomics: two runs are bitwise equal and the call captures into a HIP graph.
+ */
+size_t sc_ctc_align_workspace_bytes(int B, int T, int max_target_len);
+int sc_ctc_align(const void* x, int x_dtype, int is_logits, int B, int T, int V,
+                 int64_t stride_b, int64_t stride_t,
+                 const int64_t* targets, int64_t target_stride, int max_target_len,
+                 const int64_t* in_lens, const int64_t* tgt_lens, int blank,
+                 int32_t* states, float* frame_lp, int32_t* spans, float* token_lp, float* score,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Transducer beam search for the stateless predictor, offline and chunked (csrc/rnnt_beam.hip).

@@ -10,10 +10,10 @@ from .lucyrnn import LucyRNN, LucyRNNCell
 from .xlstm import xLSTMLarge, xLSTMLargeConfig
 from .model import (ASRModel, CTCLoss, RNNTCompactPredictorJoiner, RNNTLoss, RNNTPredictorJoiner,
                     build_lucyrnn_config, build_xlstm_config, compute_loss, detach_states)
-from .ops import (ctc_beam_decode, ctc_beam_result, ctc_beam_state, ctc_greedy_decode, ctc_loss,
-                  ctc_nll, decay_scan, lucy_scan, mlstm_chunkwise, rnnt_beam_decode, rnnt_beam_result,
-                  rnnt_beam_state, rnnt_greedy_decode, rnnt_loss)
-from .decoder import (ctc_beam_decoder, ctc_greedy_decoder, rnnt_beam_decoder,
+from .ops import (ctc_align, ctc_beam_decode, ctc_beam_result, ctc_beam_state, ctc_greedy_decode,
+                  ctc_loss, ctc_nll, decay_scan, lucy_scan, mlstm_chunkwise, rnnt_beam_decode,
+                  rnnt_beam_result, rnnt_beam_state, rnnt_greedy_decode, rnnt_loss)
+from .decoder import (ctc_beam_decoder, ctc_forced_align, ctc_greedy_decoder, rnnt_beam_decoder,
                       rnnt_greedy_decoder)
 from .streaming import StreamingLucyRNN, StreamingLucyRNNtriton
 from .frontend import make_frontend
@@ -26,4 +26,5 @@ __all__ = [
     "StreamingLucyRNN", "StreamingLucyRNNtriton", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
     "ctc_beam_decode", "ctc_beam_state", "ctc_beam_result", "ctc_beam_decoder",
     "rnnt_beam_decode", "rnnt_beam_state", "rnnt_beam_result", "rnnt_beam_decoder",
+    "ctc_align", "ctc_forced_align",
 ]

@@ -22,6 +22,7 @@
 //   rnnt_greedy_decode  (absent in the reference) greedy decode of RNNTPredictorJoiner  model.py:112-145
 //   ctc_beam_*      (absent in the reference: decoder.py is greedy only) CTC prefix beam search
 //   rnnt_beam_*     (absent in the reference) transducer beam search of RNNTPredictorJoiner
+//   ctc_align       (absent in the reference) CTC forced alignment: path, token spans, scores
 // There is no CPU kernel: calling an op on CPU tensors raises (no silent fallback).
 
 #include <ATen/ATen.h>
@@ -627,6 +628,63 @@ std::tuple<Tensor, Tensor, Tensor> ctc_beam_decode_meta(
   return {r.tokens, r.lens, r.scores};
 }
 
+// CTC forced alignment (include/statecatcher.h, sc_ctc_align): (states, labels, frame_lp, spans,
+// token_lp, score); labels = the token per frame, from states and targets with torch ops
+using AlignOut = std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor, Tensor>;
+
+void check_align(const Tensor& x, const Tensor& targets, const Tensor& in_lens,
+                 const Tensor& tgt_lens) {
+  TORCH_CHECK(x.dim() == 3, "statecatcher::ctc_align: x must be [B,T,V], got ", x.sizes());
+  TORCH_CHECK(targets.dim() == 2 && targets.size(0) == x.size(0),
+              "statecatcher::ctc_align: targets must be padded [B, U_max], got ", targets.sizes());
+  TORCH_CHECK(targets.size(1) <= 1007, "statecatcher::ctc_align: U_max = ", targets.size(1),
+              " exceeds 1007");
+  TORCH_CHECK(in_lens.numel() == x.size(0) && tgt_lens.numel() == x.size(0),
+              "statecatcher::ctc_align: in_lens/tgt_lens must have B entries");
+}
+
+AlignOut align_alloc(const Tensor& x, const Tensor& targets) {
+  const int64_t B = x.size(0), T = x.size(1), umax = targets.size(1);
+  auto io = x.options().dtype(at::kInt), fo = x.options().dtype(at::kFloat);
+  return {at::empty({B, T}, io), at::empty({B, T}, io), at::empty({B, T}, fo),
+          at::empty({B, umax, 2}, io), at::empty({B, umax}, fo), at::empty({B}, fo)};
+}
+
+AlignOut ctc_align_hip(const Tensor& x_in, const Tensor& targets_in, const Tensor& in_lens_in,
+                       const Tensor& tgt_lens_in, int64_t blank, bool is_logits) {
+  c10::DeviceGuard guard(x_in.device());
+  check_align(x_in, targets_in, in_lens_in, tgt_lens_in);
+  Tensor x = (x_in.numel() == 0 || x_in.stride(2) == 1) ? x_in : x_in.contiguous();
+  Tensor targets = targets_in.to(at::kLong).contiguous();
+  Tensor in_lens = in_lens_in.to(at::kLong).contiguous(), tgt_lens = tgt_lens_in.to(at::kLong).contiguous();
+  const int64_t B = x.size(0), T = x.size(1), V = x.size(2), umax = targets.size(1);
+  AlignOut out = align_alloc(x, targets);
+  auto& [states, labels, frame_lp, spans, token_lp, score] = out;
+  const size_t wsb = sc_ctc_align_workspace_bytes((int)B, (int)T, (int)umax);
+  Tensor ws = at::empty({(int64_t)wsb}, x.options().dtype(at::kByte));
+  sc_check(sc_ctc_align(x.data_ptr(), dtype_code(x), is_logits ? 1 : 0, (int)B, (int)T, (int)V,
+                        x.stride(0), x.stride(1), targets.data_ptr<int64_t>(),
+                        umax ? targets.stride(0) : 0, (int)umax, in_lens.data_ptr<int64_t>(),
+                        tgt_lens.data_ptr<int64_t>(), (int)blank, states.data_ptr<int32_t>(),
+                        frame_lp.data_ptr<float>(), spans.data_ptr<int32_t>(),
+                        token_lp.data_ptr<float>(), score.data_ptr<float>(), ws.data_ptr(), wsb,
+                        stream_for(x)),
+           "statecatcher::ctc_align");
+  Tensor lab = at::full_like(states, blank);
+  if (umax > 0 && T > 0) {
+    Tensor u = at::bitwise_right_shift(states.clamp_min(1) - 1, 1).to(at::kLong);
+    lab = at::where(at::bitwise_and(states, 1) == 1, targets.gather(1, u).to(at::kInt), lab);
+  }
+  labels = at::where(states >= 0, lab, at::full_like(lab, -1));
+  return out;
+}
+
+AlignOut ctc_align_meta(const Tensor& x, const Tensor& targets, const Tensor& in_lens,
+                        const Tensor& tgt_lens, int64_t blank, bool is_logits) {
+  check_align(x, targets, in_lens, tgt_lens);
+  return align_alloc(x, targets);
+}
+
 int64_t rnnt_beam_state_bytes(int64_t B, int64_t beam, int64_t max_symbols, int64_t max_frames) {
   TORCH_CHECK(B >= 0 && B <= INT32_MAX && max_frames >= 0 && max_frames <= INT32_MAX,
               "statecatcher::rnnt_beam_state_bytes: B or max_frames out of range");
@@ -1160,6 +1218,9 @@ TORCH_LIBRARY(statecatcher, m) {
   m.def("ctc_beam_decode(Tensor x, Tensor? lengths=None, Tensor? mask=None, int blank=0, "
         "int beam=8, int top_k=8, int nbest=1, bool is_logits=False, int? max_frames=None, "
         "int? cap=None) -> (Tensor tokens, Tensor lens, Tensor scores)");
+  m.def("ctc_align(Tensor x, Tensor targets, Tensor in_lens, Tensor tgt_lens, int blank=0, "
+        "bool is_logits=False) -> (Tensor states, Tensor labels, Tensor frame_lp, Tensor spans, "
+        "Tensor token_lp, Tensor score)");
   m.def("rnnt_beam_state_bytes(int B, int beam, int max_symbols, int max_frames) -> int",
         &rnnt_beam_state_bytes);
   m.def("rnnt_beam_reset_(Tensor(a!) state, int beam, int max_symbols, int max_frames, "
@@ -1199,6 +1260,7 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("ctc_beam_frames_", &ctc_beam_frames_hip);
   m.impl("ctc_beam_result", &ctc_beam_result_hip);
   m.impl("ctc_beam_decode", &ctc_beam_decode_hip);
+  m.impl("ctc_align", &ctc_align_hip);
   m.impl("rnnt_beam_reset_", &rnnt_beam_reset_hip);
   m.impl("rnnt_beam_frames_", &rnnt_beam_frames_hip);
   m.impl("rnnt_beam_result", &rnnt_beam_result_hip);
@@ -1229,6 +1291,7 @@ TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("ctc_beam_frames_", &ctc_beam_frames_meta);
   m.impl("ctc_beam_result", &ctc_beam_result_meta);
   m.impl("ctc_beam_decode", &ctc_beam_decode_meta);
+  m.impl("ctc_align", &ctc_align_meta);
   m.impl("rnnt_beam_reset_", &rnnt_beam_reset_meta);
   m.impl("rnnt_beam_frames_", &rnnt_beam_frames_meta);
   m.impl("rnnt_beam_result", &rnnt_beam_result_meta);

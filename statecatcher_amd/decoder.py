@@ -2,7 +2,7 @@
 and the transducer counterpart the reference does not have."""
 import torch
 
-from .ops import ctc_beam_decode, ctc_greedy_decode, rnnt_beam_decode, rnnt_greedy_decode
+from .ops import ctc_align, ctc_beam_decode, ctc_greedy_decode, rnnt_beam_decode, rnnt_greedy_decode
 
 
 def ctc_greedy_decoder(log_probs, input_lengths, blank=0):
@@ -31,6 +31,43 @@ def ctc_beam_decoder(log_probs, input_lengths, blank=0, beam=8, top_k=8, nbest=1
     if nbest == 1:
         hyps, scs = [h[0] if h else [] for h in hyps], [s[0] if s else float("-inf") for s in scs]
     return (hyps, scs) if return_scores else hyps
+
+
+def ctc_forced_align(log_probs, targets, input_lengths, target_lengths, blank=0, is_logits=False):
+    """CTC forced alignment of the padded transcripts targets [B,U_max] to log_probs [B,T,V]
+    (ops.ctc_align: the Viterbi path through the CTC lattice) -> one dict per stream:
+      score            the path's total log-probability (-inf: the transcript cannot be aligned)
+      score_per_frame  score / max(T_b, 1)
+      tokens           [(token, start, end, mean_lp), ...]: frames [start, end) and the mean
+                       log-probability the path takes there, per transcript token
+      labels           the token per frame (blank between tokens), T_b entries
+    An infeasible stream has empty lists.  A segment whose score_per_frame, or whose lowest
+    mean_lp, is under a threshold of the caller's choosing is a candidate hallucinated or shifted
+    transcript.  One host copy at the end."""
+    states, labels, _, spans, token_lp, score = ctc_align(log_probs, targets, input_lengths,
+                                                          target_lengths, blank, is_logits)
+    B, T = labels.shape
+    U = spans.shape[1]
+    tgt = targets.to(device=labels.device, dtype=torch.int32).reshape(B, U)
+    packed = torch.cat([score.view(torch.int32).unsqueeze(1), labels, spans.reshape(B, 2 * U),
+                        token_lp.view(torch.int32), tgt], 1).cpu()
+    scores = packed[:, 0].contiguous().view(torch.float32).tolist()
+    labs = packed[:, 1:1 + T]
+    sp = packed[:, 1 + T:1 + T + 2 * U].reshape(B, U, 2)
+    tlp = packed[:, 1 + T + 2 * U:1 + T + 3 * U].contiguous().view(torch.float32)
+    tg = packed[:, 1 + T + 3 * U:]
+    out = []
+    for b in range(B):
+        Tb = int((labs[b] >= 0).sum())
+        n = int((sp[b, :, 0] >= 0).sum())
+        if scores[b] == float("-inf"):
+            Tb = n = 0
+        toks = [(t, s, e, m) for t, (s, e), m in zip(tg[b, :n].tolist(), sp[b, :n].tolist(),
+                                                     tlp[b, :n].tolist())]
+        # (an infeasible stream has no labelled frame: -inf / 1 stays -inf)
+        out.append({"score": scores[b], "score_per_frame": scores[b] / max(Tb, 1),
+                    "tokens": toks, "labels": labs[b, :Tb].tolist()})
+    return out
 
 
 def rnnt_joiner_tables(joiner, dtype=None):

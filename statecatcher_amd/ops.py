@@ -1542,6 +1542,68 @@ def ctc_beam_decode(log_probs_or_logits, lengths=None, mask=None, blank=0, beam=
     return ctc_beam_result(state, nbest, cap, out)
 
 
+def _align_inputs(x, targets, in_lens, tgt_lens):
+    """ctc_align's inputs as the C ABI takes them -> (x, targets, in_lens, tgt_lens, B, T, V, umax)."""
+    if x.dim() != 3:
+        raise ValueError(f"ctc_align: x must be [B,T,V], got {tuple(x.shape)}")
+    B, T, V = x.shape
+    dev = x.device
+    if x.numel() and x.stride(2) != 1:
+        x = x.contiguous()
+    if targets.dim() != 2 or targets.shape[0] != B:
+        raise ValueError(f"ctc_align: targets must be padded [B, U_max], got {tuple(targets.shape)}")
+    targets = targets.to(device=dev, dtype=torch.int64).contiguous()
+    in_lens, tgt_lens = _as_len_tensor(in_lens, dev), _as_len_tensor(tgt_lens, dev)
+    if in_lens.numel() != B or tgt_lens.numel() != B:
+        raise ValueError("ctc_align: in_lens / tgt_lens must have B entries")
+    return x, targets, in_lens, tgt_lens, B, T, V, targets.shape[1]
+
+
+def align_labels(states, targets, blank=0):
+    """The token per frame of a forced alignment: int32 [B,T] from ``states`` (ctc_align) and the
+    padded ``targets`` -- blank on even states, the label on odd ones, -1 past the end.  Torch ops
+    on the device; no host sync."""
+    B, T = states.shape
+    if targets.shape[1] == 0 or T == 0:
+        lab = torch.full_like(states, int(blank))
+    else:
+        u = (states.clamp_min(1) - 1) >> 1
+        lab = torch.gather(targets.to(states.device), 1, u.to(torch.int64)).to(torch.int32)
+        lab = torch.where((states & 1) == 1, lab, torch.full_like(lab, int(blank)))
+    return torch.where(states >= 0, lab, torch.full_like(lab, -1))
+
+
+def ctc_align(x, targets, in_lens, tgt_lens, blank=0, is_logits=False):
+    """CTC forced alignment (sc_ctc_align, csrc/ctc_align.hip; the contract is in
+    include/statecatcher.h): the Viterbi path of each padded transcript targets[b, :tgt_lens[b]]
+    through x [B,T,V] (fp32 / bf16 / f16; log-probs, or logits with is_logits: the log-softmax is
+    fused), fp32 arithmetic.  Returns (states int32 [B,T], labels int32 [B,T], frame_lp fp32 [B,T],
+    spans int32 [B,U_max,2], token_lp fp32 [B,U_max], score fp32 [B]): the blank-extended state and
+    the token at every frame (-1 past in_lens), the log-probability the path takes there, each
+    token's [start, end) frames and mean log-probability, and the path's total log-probability.
+    A transcript that cannot be aligned gets score -inf, states -1 and spans -1.  No host sync (a
+    lengths list is copied to the device asynchronously); not differentiable."""
+    require_device(x)
+    x, targets, in_lens, tgt_lens, B, T, V, umax = _align_inputs(x, targets, in_lens, tgt_lens)
+    dev = x.device
+    states = torch.empty(B, T, dtype=torch.int32, device=dev)
+    frame_lp = torch.empty(B, T, dtype=torch.float32, device=dev)
+    spans = torch.empty(B, umax, 2, dtype=torch.int32, device=dev)
+    token_lp = torch.empty(B, umax, dtype=torch.float32, device=dev)
+    score = torch.empty(B, dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    wsb = lib.sc_ctc_align_workspace_bytes(B, T, umax)
+    if wsb == 0:
+        raise ValueError(f"ctc_align: U_max = {umax} exceeds 1007")
+    ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+    rc = lib.sc_ctc_align(ptr(x), dtype_code(x), 1 if is_logits else 0, B, T, V, x.stride(0),
+                          x.stride(1), ptr(targets), targets.stride(0) if umax else 0, umax,
+                          ptr(in_lens), ptr(tgt_lens), int(blank), ptr(states), ptr(frame_lp),
+                          ptr(spans), ptr(token_lp), ptr(score), ptr(ws), wsb, stream_of(x))
+    check(rc, "sc_ctc_align")
+    return states, align_labels(states, targets, blank), frame_lp, spans, token_lp, score
+
+
 class RnntBeamState(_BeamState):
     """The state of B transducer beam search streams (include/statecatcher.h, sc_rnnt_beam_*):
     ``buf`` uint8 [B, bytes per stream] holds each stream's beam, its live-frame counter, its

@@ -23,6 +23,7 @@ Reference interfaces (what a ``train.py`` user swaps in):
   rnnt_greedy_decode <- (absent in the reference) greedy decode of RNNTPredictorJoiner, model.py:112-145
   ctc_beam_decode <- (absent in the reference: decoder.py is greedy only) CTC prefix beam search
   rnnt_beam_decode <- (absent in the reference) transducer beam search of RNNTPredictorJoiner
+  ctc_align   <- (absent in the reference) CTC forced alignment: path, token spans, scores
 """
 import os
 
@@ -35,7 +36,7 @@ OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay
        "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode", "ctc_beam_state_bytes",
        "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode",
        "rnnt_beam_state_bytes", "rnnt_beam_reset_", "rnnt_beam_frames_", "rnnt_beam_result",
-       "rnnt_beam_decode")
+       "rnnt_beam_decode", "ctc_align")
 
 _LOADED = False
 
@@ -292,6 +293,13 @@ def ctc_beam_frames_(x, state, lengths=None, mask=None, blank=0, beam=8, top_k=8
 def ctc_beam_result(state, beam, nbest=1, cap=0):
     """(tokens [B,nbest,cap], lens [B,nbest], scores [B,nbest], status [B]) of a state."""
     return load().ctc_beam_result(state, beam, nbest, cap)
+
+
+def ctc_align(x, targets, in_lens, tgt_lens, blank=0, is_logits=False):
+    """(states int32 [B,T], labels int32 [B,T], frame_lp fp32 [B,T], spans int32 [B,U_max,2],
+    token_lp fp32 [B,U_max], score fp32 [B]) of the CTC forced alignment (ops.ctc_align).  Not
+    differentiable."""
+    return load().ctc_align(x, targets, in_lens, tgt_lens, blank, is_logits)
 
 
 def rnnt_beam_decode(enc_p, pred_tab, W, bias, lengths=None, mask=None, blank=0, beam=8, top_k=8,
