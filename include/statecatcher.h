@@ -838,7 +838,10 @@ size_t sc_rnnt_workspace_bytes(int B, int T, int max_labels);
  *           the packed (sum_b T_b (U_b+1), V) layout of RNNTCompactPredictorJoiner (model.py:147-200)
  *   is_logits = 1: x are joiner logits, log_softmax fused; 0: x are log-probs.
  * labels: int64 [B, max_labels] (row stride label_stride); lengths: int64 [B] device arrays.
- * nll: fp32 [B] (+inf when frames_lengths[b] == 0).  max_labels <= 1023.
+ * nll: fp32 [B].  max_labels <= 1007 (16 waves of 63 label positions).
+ * -inf log-probs or logits (a masked vocabulary) are allowed.  A sequence without an alignment
+ * (frames_lengths[b] == 0, or every path blocked by -inf entries: its final blank, or one label
+ * in every frame) gets nll = +inf and an all-zero gradient; the other sequences are unaffected.
  */
 int sc_rnnt_fwd(const void* x, int x_dtype, int is_logits, int B, int T, int max_labels, int V,
                 int64_t stride_b, int64_t stride_t, int64_t stride_u, const int64_t* row_offsets,
@@ -847,8 +850,9 @@ int sc_rnnt_fwd(const void* x, int x_dtype, int is_logits, int B, int T, int max
                 size_t workspace_bytes, void* stream);
 
 /*
- * Gradient of sum_b scale[b] * nll[b] w.r.t. x, written to grad (grad_dtype = fp32 or x_dtype,
- * same layout as x; dense rows outside the lattice are zeroed).  Logits: the softmax-corrected
+ * Gradient of sum_b scale[b] * nll[b] w.r.t. x (scale of either sign; 0 and sequences without an
+ * alignment give exact zeros), written to grad (grad_dtype = fp32 or x_dtype, same layout as x;
+ * dense rows outside the lattice are zeroed).  Logits: the softmax-corrected
  * row; log-probs: non-zero only at the blank and label entries (warp_rnnt gather=True).
  */
 int sc_rnnt_bwd(const void* x, int x_dtype, int is_logits, int B, int T, int max_labels, int V,
@@ -864,9 +868,11 @@ int sc_rnnt_bwd(const void* x, int x_dtype, int is_logits, int B, int T, int max
  *   pred  fp32 [B][U1][J]      pred_proj(embedding(blank-prefixed labels)), U1 = max_labels + 1
  *   W     bf16 [V][J]          joiner.weight (MFMA operand); bias fp32 [V] = joiner.bias
  * J must be 64 (train.py:639's --rnnt-joiner-dim default), V a multiple of 32, <= 1024.
- * Forward: nll fp32 [B] as sc_rnnt_fwd (same workspace, sc_rnnt_workspace_bytes).
- * Backward (after the forward, same workspace) of sum_b scale[b] nll[b], one pass over the
- * logits (the workgroups split the vocabulary; t_blocks and u_splits count those splits too):
+ * Forward: nll fp32 [B] as sc_rnnt_fwd (same workspace, sc_rnnt_workspace_bytes; +inf and zero
+ * gradients for a sequence without an alignment, as there).
+ * Backward (after the forward, same workspace) of sum_b scale[b] nll[b] (scale of either sign),
+ * one pass over the logits (the workgroups split the vocabulary; t_blocks and u_splits count
+ * those splits too):
  *   d_enc   fp32 [u_splits][B][T][J]   partials (sum them: d enc)
  *   d_pred  fp32 [B][t_blocks][U1][J]  partials (sum over t_blocks: d pred); zero-filled by
  *                                      the caller (columns outside the lattice are not written)

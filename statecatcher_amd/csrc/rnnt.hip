@@ -353,9 +353,16 @@ __device__ __forceinline__ void ab_run(const RnntArgs& a, int b, int Tb, int Ub)
     if (own && u == Ub) {   // log P = alpha(Tb-1, Ub) + its terminal blank (+ the shift)
       double ctot = 0.0;
       for (int q = 0; q < nw; ++q) ctot += csum[q];
-      const double lp = (double)v + (double)lpb[(int64_t)(nd - 1) * a.U1p + Ub] + off;
+      // Every path blocked (alpha(Tb-1, Ub) or the terminal blank carries the dead sentinel):
+      // no alignment exists.  The sentinel is finite, so log P would come out ~ -1e30 and the
+      // gradient kernels' al + e + be - log P would cancel it against the sentinel in alpha or
+      // beta, leaving occupancies of order 1 on live arcs.  Report what the Tb == 0 case does:
+      // nll = +inf, log P = -inf (the gradient kernels then write an all-zero row).
+      const float et = lpb[(int64_t)(nd - 1) * a.U1p + Ub];
+      const bool dead = !(v > 0.5f * kDeadR && et > 0.5f * kDeadR);
+      const double lp = dead ? -__builtin_huge_val() : (double)v + (double)et + off;
       a.ws.logp2[b] = lp;
-      a.nll[b] = (float)(-(lp + ctot) * 0.6931471805599453);
+      a.nll[b] = dead ? __builtin_huge_valf() : (float)(-(lp + ctot) * 0.6931471805599453);
     }
   }
 }
@@ -1031,6 +1038,11 @@ __global__ void __launch_bounds__(64 * kJW) joint_bwd_kernel(JointArgs a) {
     float* const prl0 = (float*)(lds + BwdLds::kPr);          // [depth][64]
     const double lp2 = r.ws.logp2[b];
     const float lsc = r.scale[b];
+    // The node weights below are formed with |scale| (p = a softmax is built as one exp2, so a
+    // must be positive); the sign of a negative upstream weight goes onto p's bf16 image and
+    // its row sum, the two places p leaves the registers.
+    const uint32_t sgn = uniform(__float_as_uint(lsc) & 0x80000000u);
+    const uint32_t sgn2 = sgn | (sgn >> 16);
     auto col_dma = [&](int uu, int bf) __attribute__((always_inline)) {
       if (w == kWp)
         dma_to_lds<4>(a.pred + ((int64_t)b * r.U1 + uu) * kJ + lane, lds_addr(prl0 + bf * 64));
@@ -1076,7 +1088,7 @@ __global__ void __launch_bounds__(64 * kJW) joint_bwd_kernel(JointArgs a) {
         const int th = lane;
         const uint32_t* nf = ndl0 + db * kNF * 32;
         float wb, wy, l2;
-        node_finish(nf, th, lp2, lsc, tb * 32 + th, uu, Tb, Ub, wb, wy, l2);
+        node_finish(nf, th, lp2, fabsf(lsc), tb * 32 + th, uu, Tb, Ub, wb, wy, l2);
         const float an = wb + wy;
         // p = a exp2(x log2e + b log2e - l2) = exp2(x log2e + b log2e + c), c = log2 a - l2
         float* ns = ns0 + bf * 128;
@@ -1174,11 +1186,12 @@ __global__ void __launch_bounds__(64 * kJW) joint_bwd_kernel(JointArgs a) {
         }
 #pragma unroll
         for (int q = 0; q < 16; ++q) ps += p[q];
-        dbs[k] += ps;
+        dbs[k] += __uint_as_float(__float_as_uint(ps) ^ sgn);
         jbf8 pf[2];
 #pragma unroll
         for (int s2 = 0; s2 < 2; ++s2) {
-          pf[s2] = pack8(p + 8 * s2);
+          typedef uint32_t ju4 __attribute__((ext_vector_type(4)));
+          pf[s2] = __builtin_bit_cast(jbf8, __builtin_bit_cast(ju4, pack8(p + 8 * s2)) ^ sgn2);
 #pragma unroll
           for (int jb = 0; jb < 2; ++jb)   // z^T fragments re-read per block (registers)
             acc[k][jb] = mfma32(pf[s2],

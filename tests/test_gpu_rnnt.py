@@ -1,7 +1,10 @@
 """GPU parity of the RNN-T loss kernels (rnnt.hip) against oracle/rnnt.py (fp64 lattice, itself
 pinned against brute-force alignment sums; warp_rnnt parity is unpinned — SURVEY §8c).
 Tolerances: nll 1e-5 relative (fp32 lattice with fp64 offsets); gradients 1e-4 relative to the
-tensor's max (fp32 rows), bf16 logits 1e-2."""
+tensor's max (fp32 rows), bf16 logits 1e-2.
+tests/test_gpu_rnnt_parity.py checks every arc at the scale of its own occupancy on every path the
+kernels take (halo widths, wave counts, diagonal counts, row paths, dtypes, sharp and masked
+emissions); tests/rnnt_cases.py holds its rule."""
 import numpy as np
 import pytest
 import torch

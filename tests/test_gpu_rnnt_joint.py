@@ -12,6 +12,11 @@ logits; W and z = tanh(enc + pred) enter the MFMA in bf16 with fp32 accumulation
 * A C5-sized lattice (T=1500, U=150, V=1024, B=2) against the unfused HIP path on materialised
   fp32 logits (the validated sc_rnnt_* kernels) with the same roundings: nll 1e-4, gradients
   1e-3 in norm; deterministic.
+* The same references slice by slice (d enc / d pred per sequence, dW / d bias per 32-row
+  vocabulary block, so a wrong block or sequence cannot hide in the tensor's norm) over the
+  kernels' geometry: one and two vocabulary splits (V <= 512 / V > 512, ragged at V = 544),
+  t-blocks of 32 frames around their edges and wholly past a sequence's frames, u-splits wider
+  than the lattice, a non-zero blank, a sequence without labels, a zero upstream weight.
 * compute_loss(mode="rnnt") with RNNTLoss runs the fused path for both joiners, DDP-safe
   (through the joiner's forward), and equals the materialised path.
 """
@@ -44,9 +49,10 @@ class _Bf16Grad(torch.autograd.Function):
         return g.to(torch.bfloat16).to(g.dtype)
 
 
-def ref_fp64(enc_p, pred_p, W, bias, labels, fl, ll, blank, round_p=False):
+def ref_fp64(enc_p, pred_p, W, bias, labels, fl, ll, blank, round_p=False, weights=None):
     """nll and gradients (enc_p, pred_p, W, bias) in fp64 with the kernels' bf16 roundings of W
-    and z; round_p: also the bf16 rounding of the dlogits that feed dW / dZ (d bias unrounded)."""
+    and z; round_p: also the bf16 rounding of the dlogits that feed dW / dZ (d bias unrounded).
+    Gradients of sum_b weights[b] nll[b] (None: the mean)."""
     e = enc_p.double().cpu().requires_grad_(True)
     p = pred_p.double().cpu().requires_grad_(True)
     w = W.double().cpu().requires_grad_(True)
@@ -66,7 +72,8 @@ def ref_fp64(enc_p, pred_p, W, bias, labels, fl, ll, blank, round_p=False):
             continue
         n, g = ornnt.rnnt_single(lp[i, :Tb, :Ub + 1].detach().numpy(), labels[i, :Ub].numpy(), blank)
         nll.append(n)
-        glp[i, :Tb, :Ub + 1] = torch.from_numpy(g) / lp.shape[0]   # mean reduction
+        glp[i, :Tb, :Ub + 1] = torch.from_numpy(g) * (1.0 / lp.shape[0] if weights is None
+                                                          else float(weights[i]))
     lp.backward(glp)
     return np.array(nll), e.grad, p.grad, w.grad, b.grad
 
@@ -119,6 +126,70 @@ def test_fused_joint_vs_fp64(B, T, Umax, V, Tb, Ub):
         # to ~0 over the vocabulary, so dZ = p W cancels and magnifies it): measured <= 1.8e-3
         assert rel(got, refq) <= 1e-3, (name, rel(got, refq))
         assert rel(got, ref) <= 5e-3, (name, rel(got, ref))
+
+
+def slice_rels(got, ref, dim_slices):
+    """Relative error in norm of every slice; a slice whose reference is exactly zero must be
+    exactly zero (reported as 0 or inf)."""
+    out = []
+    for sl in dim_slices:
+        g, r = got[sl].double().cpu(), ref[sl].double().cpu()
+        if float(r.norm()) == 0.0:
+            out.append(0.0 if not g.any() else float("inf"))
+        else:
+            out.append(float((g - r).norm() / r.norm()))
+    return out
+
+
+_V5 = [(2, 9, 4, V, [9, 6], [4, 2], 0, None) for V in (160, 512, 544, 800, 1024)]
+_T4 = [(2, T, 2, 64, [T, T - 2], [2, 1], 0, None) for T in (31, 32, 33, 65)]
+_U5 = [(2, 9, U, 64, [9, 7], [U, U // 2], 0, None) for U in (0, 2, 4, 8, 9)]
+SLICE_CASES = _V5 + _T4 + _U5 + [
+    (2, 70, 3, 64, [70, 20], [3, 2], 0, None),          # t-blocks 1 and 2 lie past Tb = 20
+    (2, 9, 4, 64, [9, 6], [4, 2], 33, None),            # non-zero blank, mid-block
+    (2, 9, 4, 64, [9, 6], [4, 2], 63, None),            # blank = V - 1
+    (2, 9, 4, 544, [9, 6], [4, 2], 543, None),          # ... in the ragged second split
+    (2, 9, 4, 64, [9, 6], [4, 0], 0, None),             # a sequence without labels
+    (2, 9, 4, 64, [9, 6], [4, 2], 0, [1.0, 0.0]),       # zero upstream weight: an exactly zero row
+    (2, 9, 4, 1024, [9, 6], [4, 2], 0, [-0.5, 1e3]),
+]
+
+
+@pytest.mark.parametrize("B,T,Umax,V,Tb,Ub,blank,w", SLICE_CASES)
+def test_fused_joint_slices_vs_fp64(B, T, Umax, V, Tb, Ub, blank, w):
+    """Every sequence's d enc / d pred and every 32-row vocabulary block of dW / d bias against
+    fp64: 1e-3 in norm with the kernels' roundings, 5e-3 plain (the numbers of
+    test_fused_joint_vs_fp64, applied per slice)."""
+    joiner, enc_out, labels, fl, ll = case(B, T, Umax, V, 7 * T + Umax + V + blank, Tb, Ub)
+    labels[labels == blank] = 0 if blank else 1
+    joiner = joiner.to(DEV)
+    prefix = torch.cat([torch.zeros(B, 1, dtype=torch.long), labels], 1).to(DEV)
+    enc_p, pred_p, W, bias = (t.detach().requires_grad_(True)
+                              for t in joiner(enc_out.to(DEV), prefix, project_only=True))
+    nll = sc().ops.RNNTJointFn.apply(enc_p, pred_p, W, bias, labels.to(DEV), fl.to(DEV), ll.to(DEV),
+                                     blank)
+    wt = torch.tensor(w if w is not None else [1.0 / B] * B)
+    (nll * wt.to(DEV)).sum().backward()
+    args = (enc_p.detach(), pred_p.detach(), W.detach(), bias.detach(), labels, fl, ll, blank)
+    rn, *plain = ref_fp64(*args, weights=wt)
+    _, *rounded = ref_fp64(*args, round_p=True, weights=wt)
+    np.testing.assert_allclose(nll.detach().cpu().numpy(), rn, rtol=1e-4)
+    per_seq = [(slice(b, b + 1),) for b in range(B)]
+    per_blk = [(slice(v, v + 32),) for v in range(0, V, 32)]
+    worst = {}
+    for got, ref, refq, name, sls in zip([enc_p.grad, pred_p.grad, W.grad, bias.grad], plain, rounded,
+                                         ["enc", "pred", "W", "bias"],
+                                         [per_seq, per_seq, per_blk, per_blk]):
+        assert torch.isfinite(got).all(), name
+        rq, rp = slice_rels(got, refq, sls), slice_rels(got, ref, sls)
+        worst[name] = (max(rq), max(rp))
+        assert max(rq) <= 1e-3, (name, "rounded reference", rq)
+        assert max(rp) <= 5e-3, (name, "plain fp64", rp)
+    print(f"fused joint slices T={T} U={Umax} V={V} blank={blank} w={w}: worst slice (rounded, "
+          "plain) " + ", ".join(f"{k} {a:.1e} {b:.1e}" for k, (a, b) in worst.items()))
+    if w is not None and 0.0 in w:
+        z = w.index(0.0)
+        assert not enc_p.grad[z].any() and not pred_p.grad[z].any()
 
 
 def test_fused_joint_zero_frames_is_inf():
