@@ -824,6 +824,35 @@ int sc_mlstm_gate_bwd(const float* qdq, const float* kdk, const float* fgate, in
                       float* dfgate, const void* a, void* da, int NH, int64_t ld, int io, int fo,
                       float cap, void* stream);
 
+/* 1 if the mLSTM step kernel is compiled for this operand dtype (fp32/bf16) and head dims. */
+int sc_mlstm_step_supported(int io_dtype, int DQ, int DV);
+
+/*
+ * The recurrent mLSTM step (streaming / any-length inference): advances BH = batch x heads
+ * sequences by K steps from the carried state, in fp32 arithmetic:
+ *   m_t = max(logsig(f_t) + m_{t-1}, i_t)
+ *   C_t = e^{logsig(f_t)+m_{t-1}-m_t} C_{t-1} + e^{i_t-m_t} k_t v_t^T      (n_t alike)
+ *   h_t = (q~_t C_t) / (max(|q~_t . n_t|, e^{-m_t}) + eps),  q~ = q DQ^-1/2.
+ * State C fp32 [BH][DQ][DV], n [BH][DQ], m [BH]: sc_mlstm_fwd's c_last / states_n[:, T/64] /
+ * states_m[:, T/64] convention (no conversion between the two kernels), updated IN PLACE; it is
+ * read once and written once per call whatever K is (C stays in registers over the K steps).
+ * q, k [BH][K][DQ], v [BH][K][DV] in io_dtype (fp32 or bf16); h [BH][K][DV] in io_dtype.
+ * layout: as sc_mlstm_fwd's (7 int64 {NH, qb, qh, qt, vb, vh, vt}, layout[0] == NH; NULL =
+ * contiguous), the same stride and alignment rules.
+ * Gates: gate_layout == NULL: igate, fgate fp32 [BH][K] pre-activations.  Else 3 int64
+ * {gb, gh, gt}: igate / fgate point into the projection (io_dtype) and sequence bh = b NH + h
+ * reads step t at b gb + h gh + t gt.  Either way the soft cap cap tanh(x / cap) is applied in
+ * fp32 when cap > 0 (cap <= 0: none).
+ * live: optional fp32 [BH / NH][K]; a step with live == 0 leaves C, n, m bitwise untouched and
+ * writes a zero output row.  NULL = all live.
+ * A step's arithmetic does not depend on K or its position in the call: K steps in one call
+ * equal K calls of one step bitwise.  K == 0 or BH == 0: no-op.
+ */
+int sc_mlstm_step(const void* q, const void* k, const void* v, int io_dtype, const void* igate,
+                  const void* fgate, const int64_t* gate_layout, float cap, const float* live,
+                  float* C, float* n, float* m, int BH, int K, int NH, int DQ, int DV, float eps,
+                  void* h, const int64_t* layout, void* stream);
+
 /* ---------------------------------------------------------------- RNN-T ----------------- */
 
 /* Workspace bytes for sc_rnnt_fwd / sc_rnnt_bwd (gathered log-probs, alpha, beta, offsets). */

@@ -277,7 +277,9 @@ class ASRModel(nn.Module):
     def forward(self, feats, mask, states=None):
         if hasattr(self, "proj"):
             feats = self.proj(feats)
-        if isinstance(self.encoder, xLSTMLarge):
+        if isinstance(self.encoder, xLSTMLarge) and self.encoder.config.mode != "inference":
+            # (mode="inference" takes any T: its remainder runs on the step kernel, and zero
+            # frames would advance the carried state)
             # model.py:341-347: pad time to the 64-step chunk.  The reference then multiplies by
             # the UNPADDED mask (a broadcast error whenever T % 64 != 0); the mask is padded
             # with zeros here so padded frames are zero, as intended.

@@ -2212,6 +2212,120 @@ def mlstm_chunkwise(query, key, value, igate, fgate, c_initial=None, n_initial=N
     return (h, (c, n, m)) if return_last_states else h
 
 
+def mlstm_step_supported(dtype, DQ, DV):
+    """True where sc_mlstm_step is compiled: fp32 / bf16 operands, the mLSTM cell's head dims."""
+    if dtype not in (torch.float32, torch.bfloat16):
+        return False
+    return bool(_lib.load().sc_mlstm_step_supported(_lib._DTYPE[dtype], int(DQ), int(DV)))
+
+
+def _mlstm_step_state(C, n, m, B, NH, DQ, DV, dev):
+    """The carried state as sc_mlstm_step takes it: fp32, contiguous, on the operands' device,
+    C [B,NH,DQ,DV], n [B,NH,DQ], m [B,NH,1] or [B,NH].  It is updated in place, so nothing is
+    cast or copied here: a wrong dtype or layout raises."""
+    for name, t, shape in (("C", C, (B, NH, DQ, DV)), ("n", n, (B, NH, DQ)), ("m", m, (B, NH))):
+        got = tuple(t.shape[:-1]) if name == "m" and t.dim() == 3 and t.shape[-1] == 1 \
+            else tuple(t.shape)
+        if got != shape:
+            raise ValueError(f"mlstm_step: state {name} has shape {tuple(t.shape)}, expected {shape}")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"mlstm_step: state {name} must be a contiguous fp32 tensor on {dev} "
+                             "(it is updated in place)")
+
+
+def _mlstm_step_live(live, B, K, dev):
+    if live is None:
+        return None
+    if tuple(live.shape) != (B, K):
+        raise ValueError(f"mlstm_step: live has shape {tuple(live.shape)}, expected {(B, K)}")
+    return live.to(dev, torch.float32).contiguous()
+
+
+@torch.no_grad()
+def mlstm_step(q, k, v, igate, fgate, C, n, m, live=None, eps=1e-6, cap=None):
+    """The recurrent mLSTM step (csrc/mlstm_step.hip): q, k [B,NH,K,DQ], v [B,NH,K,DV] (fp32 or
+    bf16), gate pre-activations [B,NH,K] (soft-capped here in fp32 when ``cap`` is given, else
+    taken as they are) advance the state C [B,NH,DQ,DV], n [B,NH,DQ], m [B,NH,1] IN PLACE by K
+    steps and return h [B,NH,K,DV] in q's dtype.  live [B,K]: steps with 0 hold the state and
+    return a zero row.  The state convention is mlstm_chunkwise's last state.  No gradient."""
+    require_device(q, k, v, igate, fgate, C, n, m)
+    B, NH, K, DQ = q.shape
+    DV = v.shape[-1]
+    if q.dtype not in (torch.float32, torch.bfloat16) or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise TypeError(f"mlstm_step: q / k / v must share fp32 or bf16, got {q.dtype}, {k.dtype}, "
+                        f"{v.dtype}")
+    if k.shape != q.shape or tuple(v.shape[:3]) != (B, NH, K):
+        raise ValueError("mlstm_step: q, k [B,NH,K,DQ] and v [B,NH,K,DV] disagree")
+    if not mlstm_step_supported(q.dtype, DQ, DV):
+        raise ValueError(f"mLSTM step head dims (DQ={DQ}, DV={DV}) not compiled in")
+    _mlstm_step_state(C, n, m, B, NH, DQ, DV, q.device)
+    lv = _mlstm_step_live(live, B, K, q.device)
+    qc, kc, vc = q.contiguous(), k.contiguous(), v.contiguous()
+    ig = igate.float().contiguous().view(B * NH, K)
+    fg = fgate.float().contiguous().view(B * NH, K)
+    h = torch.empty(B, NH, K, DV, dtype=q.dtype, device=q.device)
+    check(_lib.load().sc_mlstm_step(ptr(qc), ptr(kc), ptr(vc), dtype_code(qc), ptr(ig), ptr(fg), None,
+                                    float(cap) if cap is not None else 0.0, ptr(lv), ptr(C), ptr(n),
+                                    ptr(m), B * NH, K, NH, DQ, DV, float(eps), ptr(h), None,
+                                    stream_of(qc)), "sc_mlstm_step")
+    return h
+
+
+def mlstm_step_inplace_ok(a, NH, DQ, DV):
+    """The strided reads of mlstm_step_proj: a [B,K,N] contiguous fp32 / bf16 with every row piece
+    on the kernels' 8-element / 16-byte grid (sc_mlstm_fwd's layout rules)."""
+    return (a.dim() == 3 and a.is_contiguous() and a.shape[2] % 8 == 0 and DQ % 8 == 0
+            and DV % 8 == 0 and a.data_ptr() % 16 == 0)
+
+
+@torch.no_grad()
+def mlstm_step_proj(a, C, n, m, NH, DQ, DV, cap=None, o_norm=None, live=None, eps=1e-6,
+                    eps_mh=1e-6):
+    """mlstm_step on the xLSTM layer's fused projection a = [q | k | v | o | i | f] [B,K,N] (fp32
+    or bf16): q / k / v and the raw gate pre-activations are read in place (layout strides; the
+    soft cap is applied inside the kernel in fp32), the state advances in place.  Returns h
+    [B,NH,K,DV], or with o_norm = the MultiHeadLayerNorm weight, y = sigmoid(o) *
+    MultiHeadLayerNorm(h) * w [B,K,NH*DV] (sc_mhln_gate_fwd on bf16 where it applies, else the
+    torch chain of xlstm.MultiHeadLayerNorm).  A projection whose row pieces are off the 8-element
+    grid (N % 8 != 0) goes through contiguous copies of q / k / v instead."""
+    require_device(a, C, n, m)
+    B, K, N = a.shape
+    if N != 2 * NH * DQ + 2 * NH * DV + 2 * NH:
+        raise ValueError(f"mlstm_step_proj: projection width {N} is not [q|k|v|o|i|f] for NH={NH}, "
+                         f"DQ={DQ}, DV={DV}")
+    if not mlstm_step_supported(a.dtype, DQ, DV):
+        raise ValueError(f"mLSTM step: dtype {a.dtype} / head dims (DQ={DQ}, DV={DV}) not compiled in")
+    ko, vo = NH * DQ, 2 * NH * DQ
+    oo = vo + NH * DV
+    io, fo = oo + NH * DV, oo + NH * DV + NH
+    if mlstm_step_inplace_ok(a, NH, DQ, DV):
+        _mlstm_step_state(C, n, m, B, NH, DQ, DV, a.device)
+        lv = _mlstm_step_live(live, B, K, a.device)
+        esz, base = a.element_size(), a.data_ptr()
+        lay = (ctypes.c_int64 * 7)(NH, K * N, DQ, N, K * N, DV, N)
+        glay = (ctypes.c_int64 * 3)(K * N, 1, N)
+        h = torch.empty(B, NH, K, DV, dtype=a.dtype, device=a.device)
+        check(_lib.load().sc_mlstm_step(base, base + ko * esz, base + vo * esz, dtype_code(a),
+                                        base + io * esz, base + fo * esz, glay,
+                                        float(cap) if cap is not None else 0.0, ptr(lv), ptr(C),
+                                        ptr(n), ptr(m), B * NH, K, NH, DQ, DV, float(eps), ptr(h),
+                                        lay, stream_of(a)), "sc_mlstm_step")
+    else:
+        q = a[..., :ko].reshape(B, K, NH, DQ).transpose(1, 2)
+        k = a[..., ko:vo].reshape(B, K, NH, DQ).transpose(1, 2)
+        v = a[..., vo:oo].reshape(B, K, NH, DV).transpose(1, 2)
+        h = mlstm_step(q, k, v, a[..., io:fo].transpose(1, 2), a[..., fo:].transpose(1, 2), C, n, m,
+                       live=live, eps=eps, cap=cap)
+    if o_norm is None:
+        return h
+    o = a[..., oo:io]
+    if a.dtype == torch.bfloat16 and gated_head_norm_supported(h):
+        return gated_head_norm(h, o, o_norm, eps_mh)
+    y = h.transpose(1, 2).float()
+    y = (y - y.mean(-1, keepdim=True)) * torch.rsqrt(y.var(-1, keepdim=True, unbiased=False) + eps_mh)
+    return torch.sigmoid(o) * (y.to(a.dtype).reshape(B, K, NH * DV) * o_norm)
+
+
 # ----------------------------------------------------------------------------- xLSTM glue ----
 def _part_sum(part):
     """fixed-order fp32 sum of the [P, D] weight-gradient partial rows (sc_colsum)."""

@@ -206,7 +206,7 @@ class _StreamBase:
         (and logits [B, T', V] if asked).  One host sync at the end.  With beam: the best
         hypothesis of every stream since its reset."""
         B, T, F = feats.shape
-        k = self.cfg.stack_order
+        k = getattr(self.cfg, "stack_order", 1)   # (the xLSTM config has none: 1)
         Tt = T - T % k
         x = feats[:, :Tt].reshape(B, Tt // k, F * k)
         m = None
@@ -621,3 +621,115 @@ class StreamingLucyRNNtriton(_StreamBase):
         """([[h] * L], [[s] * L]) fp32 copies: LucyRNNtriton.forward's ``hidden_states``."""
         h, s = super().state()
         return [h], [s]
+
+
+class StreamingXLSTM(_StreamBase):
+    """Decode ``batch`` concurrent streams through an xLSTMLarge (xlstm.py; weights snapshotted at
+    construction) ``frames_per_call`` frames per call.
+
+    A block is xLSTMLarge.step on static buffers: per xLSTM block the fused projection GEMM, ONE
+    recurrent mLSTM launch for the block's K frames (csrc/mlstm_step.hip: the matrix state C is
+    read once, held in registers over the K steps and written once, in place), the gated head
+    norm, out_proj, the residual / RMSNorm glue and the FFN; then out_norm, lm_head, the logit
+    soft cap, and the greedy CTC / transducer tail of the LucyRNN streamers.  It is a linear
+    chain of launches, captured once as a hipGraph.
+
+    dtype: the weight and GEMM dtype; activations between kernels are what the offline model has
+    under the same dtype (bf16 under bf16 autocast, fp32 without).  State: {block: (C [B,NH,DQ,DV],
+    n [B,NH,DQ], m [B,NH,1])} fp32, the dict xLSTMLarge.forward returns and takes: reset(states)
+    and state() hand over between an offline segment and the stream.  Frames with mask 0 hold
+    every block's state and emit nothing -- where the offline model, padded to a 64-frame chunk
+    with zero frames, advances its state through the padding.
+    input_proj: an nn.Linear applied before the encoder's embedding (an ASRModel's ``proj``).
+    gemm: "frame" runs the linears on lucy_frame_gemm (csrc/lucy_frame.hip), whose arithmetic per
+    row does not depend on the block size: a block of K frames equals K calls of one frame
+    bitwise.  "library" runs the library GEMM autocast would run (it picks its kernel by the row
+    count, so block sizes agree to rounding only).  "auto": "frame" where its limits hold (every
+    reduction length a multiple of 8 and <= 2048), else "library".
+    """
+
+    engine = "frame"     # (the transducer tail's enc_proj runs on lucy_frame_gemm)
+    schedule = "frame"
+
+    def __init__(self, model, batch: int, frames_per_call: int = 1, dtype=torch.bfloat16,
+                 graph: bool = True, blank: int = 0, joiner=None, max_symbols: int = 4, beam=None,
+                 top_k: int = 8, nbest: int = 1, max_frames: int = 4096, input_proj=None,
+                 gemm: str = "auto"):
+        import copy
+
+        from .xlstm import xLSTMLarge
+        if not isinstance(model, xLSTMLarge):
+            raise TypeError(f"StreamingXLSTM streams an xLSTMLarge, got {type(model).__name__}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("streaming: weights fp32 or bf16")
+        cfg = model.config
+        dev = next(model.parameters()).device
+        ops._lib.require_device(next(model.parameters()))
+        NH = cfg.num_heads
+        lay = model.blocks[0].mlstm_layer
+        if not ops.mlstm_step_supported(dtype, lay.qk_dim // NH, lay.v_dim // NH):
+            raise ValueError(f"streaming: mLSTM step head dims (DQ={lay.qk_dim // NH}, "
+                             f"DV={lay.v_dim // NH}) not compiled in")
+        self.cfg, self.B, self.K, self.dtype, self.blank = cfg, batch, frames_per_call, dtype, blank
+        self.L, self.V = cfg.num_blocks, cfg.vocab_size
+        self.stack_order = 1
+        B, K = batch, frames_per_call
+        # the snapshot: a private copy of the module (its norms' fp32 parameters) and every
+        # linear weight cast to dtype once
+        self.model = copy.deepcopy(model).eval().requires_grad_(False)
+        # gemm="frame": the linears on lucy_frame_gemm, whose arithmetic per row does not depend
+        # on the block size (K frames per call == K calls of one frame bitwise); "library": the
+        # library GEMM, which picks its kernel by the row count (equal to rounding only)
+        if gemm == "auto":
+            gemm = "frame" if self.model.step_gemm_frame_ok(input_proj) else "library"
+        self.gemm = gemm
+        self.weights = self.model.step_weights(dtype, input_proj, gemm)
+        self.Din = (input_proj.in_features if input_proj is not None
+                    else self.model.embedding.in_features)
+        self.joiner = joiner is not None
+        if beam is not None and not self.joiner:
+            raise ValueError("beam= needs a joiner (the beam search is the transducer's)")
+        if self.joiner:
+            self._init_joiner(joiner, max_symbols, dev, beam, top_k, nbest, max_frames)
+        f32 = torch.float32
+        self.x = torch.zeros(K, B, self.Din, dtype=f32, device=dev)
+        self.mask = torch.ones(K, B, dtype=f32, device=dev)
+        self.states = self.model.zero_state(B, dev)
+        self.logits = torch.zeros(K, B, self.V, dtype=f32, device=dev)
+        self.emit = torch.full((K, B), -1, dtype=torch.int32, device=dev)
+        self.prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        if self.joiner:
+            self.enc_p = torch.zeros(K, B, self.J, dtype=f32, device=dev)
+        self.graph = None
+        if graph:
+            self._capture()
+        self.reset()
+
+    def _block(self):
+        logits, _ = self.model.step(self.x.transpose(0, 1), self.states, self.mask.t(),
+                                    self.weights)
+        self.logits.copy_(logits.transpose(0, 1))
+        if self.joiner:
+            return self._rnnt_block()
+        ops.ctc_greedy_frames(self.logits, self.prev, self.emit, mask=self.mask, blank=self.blank)
+
+    # ------------------------------------------------------------------------------- API ---
+    def reset(self, states=None, streams=None):
+        """Start streams afresh: state from ``states`` ({block: (C, n, m)}, what
+        xLSTMLarge.forward returns; a missing block or entry is zero) or zero, prev token = none
+        (``blank`` with a joiner).  ``streams``: the streams to reset (default all)."""
+        idx = slice(None) if streams is None else torch.as_tensor(streams, device=self.x.device)
+        for i, bufs in self.states.items():
+            src = None if states is None else states.get(i)
+            for j, buf in enumerate(bufs):
+                if src is None or src[j] is None:
+                    buf[idx] = 0.0
+                else:
+                    buf[idx] = src[j].detach().to(buf.device, torch.float32).reshape(buf.shape)[idx]
+        self.prev[idx] = self.blank if self.joiner else -1
+        if self.beam is not None:
+            self.beam_state.reset(None if streams is None else torch.as_tensor(streams).tolist())
+
+    def state(self):
+        """{block: (C, n, m)} fp32 copies: xLSTMLarge.forward's ``state``."""
+        return {i: tuple(t.clone() for t in st) for i, st in self.states.items()}

@@ -15,8 +15,15 @@ xLSTM-large architecture as transformers 5.15.0 restates it
           ``embedding``), blocks, out_norm, lm_head, logits softcap(30)
 
 Recurrent state: {block index: (C [B,NH,DQ,DV], n [B,NH,DQ], m [B,NH,1])}, carried across
-segments like LucyRNNtriton's (detach_states handles dicts).  Sequences must be a multiple of
-the 64-step chunk: ASRModel pads to 64 exactly as the reference does (model.py:341-347).
+segments like LucyRNNtriton's (detach_states handles dicts).  In mode="train" sequences must be
+a multiple of the 64-step chunk: ASRModel pads to 64 exactly as the reference does
+(model.py:341-347).
+
+mode="inference" (no gradient) takes any T as the xlstm package's inference wrapper does
+(modeling_xlstm.py wrap_chunkwise_arbitrary_sequence_length): whole chunks on the chunkwise
+kernel, the remainder on the recurrent step kernel (csrc/mlstm_step.hip) from the state the
+chunks leave.  ``step`` runs K frames on the step kernel alone with the state in place: what
+streaming.StreamingXLSTM replays per block.
 """
 from dataclasses import dataclass
 from typing import Optional
@@ -151,6 +158,32 @@ class FeedForward(nn.Module):
         g, u = a.split([up, up], -1)
         return self.proj_down(F.silu(g) * u)
 
+    def step_weights(self, dtype, frame=False):
+        """The step path's snapshot: [proj_up_gate | proj_up] concatenated and proj_down, cast to
+        ``dtype`` once (frame: as mLSTMLayer.step_weights)."""
+        cat = lambda a, b: None if a is None else torch.cat([a.detach(), b.detach()])  # noqa: E731
+        w_up = cat(self.proj_up_gate.weight, self.proj_up.weight).to(dtype)
+        dev = w_up.device
+        return {"w_up": w_up, "frame": frame,
+                "b_up": _step_bias(cat(self.proj_up_gate.bias, self.proj_up.bias), w_up.shape[0],
+                                   dtype, frame, dev),
+                "w_down": self.proj_down.weight.detach().to(dtype).contiguous(),
+                "b_down": _step_bias(self.proj_down.bias, self.proj_down.weight.shape[0], dtype,
+                                     frame, dev)}
+
+    @torch.no_grad()
+    def step(self, x, weights):
+        """forward() on a step_weights() snapshot (no per-call weight casts, no autograd)."""
+        w = weights
+        a = _step_linear(x, w["w_up"], w["b_up"], w["frame"])
+        up = a.shape[-1] // 2
+        if a.is_cuda and a.dtype == torch.bfloat16 and up % 4 == 0:
+            y = ops.swiglu(a)
+        else:
+            g, u = a.split([up, up], -1)
+            y = F.silu(g) * u
+        return _step_linear(y, w["w_down"], w["b_down"], w["frame"])
+
 
 class mLSTMLayer(nn.Module):
     def __init__(self, cfg: xLSTMLargeConfig):
@@ -243,6 +276,93 @@ class mLSTMLayer(nn.Module):
         return self.out_proj(torch.sigmoid(o) * h), new_state
 
 
+    # ---------------------------------------------------------------------- step path ---
+    def step_weights(self, dtype, frame=False):
+        """The layer's weights as the step path reads them: the six projections concatenated and
+        cast to ``dtype`` once (what autocast casts per call), out_proj alike, the head-norm
+        weight in fp32.  Detached: a snapshot, as a streaming decoder keeps it.  frame: the
+        GEMMs run on ops.lucy_frame_gemm (_step_linear)."""
+        mh = self.multihead_norm
+        if mh.bias is not None or not mh.force_float32_reductions:
+            raise ValueError("the mLSTM step path needs use_bias=False and fp32 norm reductions")
+        mods = self._mods()
+        b = None
+        if any(m.bias is not None for m in mods):
+            b = torch.cat([m.bias.detach() if m.bias is not None else
+                           _zeros(m.weight.shape[0], m.weight.dtype, m.weight.device)
+                           for m in mods])
+        w = torch.cat([m.weight.detach() for m in mods]).to(dtype)
+        dev = w.device
+        return {"w": w, "b": _step_bias(b, w.shape[0], dtype, frame, dev), "frame": frame,
+                "w_mh": mh.weight.detach().float().contiguous(),
+                "w_out": self.out_proj.weight.detach().to(dtype).contiguous(),
+                "b_out": _step_bias(self.out_proj.bias, self.out_proj.weight.shape[0], dtype,
+                                    frame, dev)}
+
+    def zero_state(self, B, device):
+        """(C, n, m) zeros for B streams: the state a sequence starts from."""
+        NH = self.cfg.num_heads
+        DQ, DV = self.qk_dim // NH, self.v_dim // NH
+        z = dict(dtype=torch.float32, device=device)
+        return (torch.zeros(B, NH, DQ, DV, **z), torch.zeros(B, NH, DQ, **z),
+                torch.zeros(B, NH, 1, **z))
+
+    @torch.no_grad()
+    def step(self, x, state, live=None, weights=None):
+        """K frames x [B,K,d] through the layer on the recurrent step kernel
+        (csrc/mlstm_step.hip): fused projection, ops.mlstm_step_proj with ``state`` = (C, n, m)
+        fp32 advanced IN PLACE, sigmoid(o) * MultiHeadLayerNorm(h), out_proj.  live [B,K]:
+        frames with 0 hold the state.  Any K, no gradient.  ``weights``: a step_weights()
+        snapshot (default: taken now, in the autocast dtype if autocast is on, else x's)."""
+        if weights is None:
+            weights = self.step_weights(_step_dtype(x))
+        w = weights
+        NH = self.cfg.num_heads
+        a = _step_linear(x, w["w"], w["b"], w["frame"])
+        C, n, m = state
+        y = ops.mlstm_step_proj(a, C, n, m, NH, self.qk_dim // NH, self.v_dim // NH,
+                                cap=self.cfg.gate_soft_cap, o_norm=w["w_mh"], live=live,
+                                eps=self.cfg.eps, eps_mh=self.multihead_norm.eps)
+        return _step_linear(y, w["w_out"], w["b_out"], w["frame"])
+
+
+def step_gemm_frame_ok(*ks):
+    """ops.lucy_frame_gemm's limits on a GEMM's reduction length (bf16 weights: a multiple of 8;
+    the input rows live in LDS: at most 2048)."""
+    return all(k % 8 == 0 and k <= 2048 for k in ks)
+
+
+def _step_bias(b, n, dtype, frame, device):
+    """A snapshot's bias: in the weight dtype for the library GEMM (None stays None), fp32 and
+    never None for ops.lucy_frame_gemm."""
+    if not frame:
+        return None if b is None else b.detach().to(dtype)
+    return (torch.zeros(n, dtype=torch.float32, device=device) if b is None
+            else b.detach().float().contiguous())
+
+
+def _step_linear(x, w, b, frame):
+    """x W^T + b on the step path, output in the weight dtype.  frame=False: the library GEMM on
+    x cast to the weight dtype (what autocast does).  frame=True: ops.lucy_frame_gemm
+    (csrc/lucy_frame.hip, MFMA on fp32 activations with fp32 accumulation): a row's arithmetic
+    does not depend on how many rows the call has, so a block of K frames equals K single
+    frames bitwise -- the library picks its kernel by the row count."""
+    if not frame:
+        return F.linear(x.to(w.dtype), w, b)
+    x2 = x.to(w.dtype).reshape(-1, x.shape[-1]).float().contiguous()
+    y = torch.empty(x2.shape[0], w.shape[0], dtype=torch.float32, device=x.device)
+    ops.lucy_frame_gemm(ops.FRAME_PLAIN, x2, w, b, y)
+    return y.view(*x.shape[:-1], w.shape[0]).to(w.dtype)
+
+
+def _step_dtype(x):
+    """The step path's weight / activation dtype when no snapshot is given: the autocast dtype
+    under autocast (what the chunkwise path's linears compute in), else x's own."""
+    if x.is_cuda and torch.is_autocast_enabled("cuda"):
+        return torch.get_autocast_dtype("cuda")
+    return x.dtype
+
+
 def _add_norm(x, y, norm):
     """(x + y, norm(x + y)): the block's residual add and the RMSNorm that reads its result as
     one HIP pass (ops.AddRMSNormFn, bf16 roundings as the torch chain) where the glue kernels
@@ -285,7 +405,116 @@ class xLSTMLarge(nn.Module):
                          if config.add_out_norm else nn.Identity())
         self.lm_head = nn.Linear(config.embedding_dim, config.vocab_size, bias=False)
 
+    # ---------------------------------------------------------------------- step path ---
+    def step_gemm_frame_ok(self, input_proj=None):
+        """Whether every GEMM of step() fits ops.lucy_frame_gemm (step_weights(gemm="frame"))."""
+        lay, ffn = self.blocks[0].mlstm_layer, self.blocks[0].ffn
+        ks = [self.embedding.in_features, self.config.embedding_dim, lay.v_dim,
+              ffn.proj_down.in_features]
+        if input_proj is not None:
+            ks.append(input_proj.in_features)
+        return step_gemm_frame_ok(*ks)
+
+    def step_weights(self, dtype, input_proj=None, gemm="library"):
+        """Every linear weight of the encoder cast to ``dtype`` once, for step(): a snapshot (a
+        streaming decoder takes it at construction).  input_proj: an nn.Linear applied before the
+        embedding (ASRModel.proj).  The norms keep their fp32 parameters.  gemm: "library" (the
+        GEMMs autocast would run) or "frame" (ops.lucy_frame_gemm: block-size invariant
+        arithmetic, _step_linear; fp32 / bf16, reduction lengths % 8 == 0 and <= 2048)."""
+        if gemm not in ("library", "frame"):
+            raise ValueError('gemm must be "library" or "frame"')
+        frame = gemm == "frame"
+        if frame and not (self.step_gemm_frame_ok(input_proj)
+                          and dtype in (torch.float32, torch.bfloat16)):
+            raise ValueError('gemm="frame" needs fp32 / bf16 weights and every reduction length '
+                             'a multiple of 8, at most 2048; use gemm="library"')
+        cast = lambda t: t.detach().to(dtype).contiguous()   # noqa: E731
+        dev = self.embedding.weight.device
+        bias = lambda m: _step_bias(m.bias, m.weight.shape[0], dtype, frame, dev)   # noqa: E731
+        w = {"w_emb": cast(self.embedding.weight), "b_emb": bias(self.embedding),
+             "w_lm": cast(self.lm_head.weight), "b_lm": bias(self.lm_head), "dtype": dtype,
+             "frame": frame,
+             "blocks": [{"mlstm": blk.mlstm_layer.step_weights(dtype, frame),
+                         "ffn": blk.ffn.step_weights(dtype, frame)} for blk in self.blocks]}
+        if input_proj is not None:
+            w["w_in"], w["b_in"] = cast(input_proj.weight), bias(input_proj)
+        return w
+
+    def zero_state(self, B, device=None):
+        """{block: (C, n, m)} zeros for B streams."""
+        device = self.embedding.weight.device if device is None else device
+        return {i: blk.mlstm_layer.zero_state(B, device) for i, blk in enumerate(self.blocks)}
+
+    @torch.no_grad()
+    def step(self, x, state=None, live=None, weights=None):
+        """K frames x [B,K,input_dim] through the whole encoder on the recurrent step kernel: any
+        K >= 1, state {block: (C, n, m)} fp32 advanced IN PLACE (None: zeros are made) and
+        returned with the logits [B,K,V].  live [B,K]: frames with 0 hold every block's state
+        (their logits are not meaningful).  Everything but the cell is per frame and is
+        forward()'s code: the RMSNorm / residual glue, the linears on a snapshot of the weights
+        (``weights`` = step_weights(); default: taken now, in the autocast dtype under autocast,
+        else x's dtype).  No gradient."""
+        w = self.step_weights(_step_dtype(x)) if weights is None else weights
+        dt = w["dtype"]
+        if state is None:
+            state = self.zero_state(x.shape[0], x.device)
+        with torch.autocast("cuda", enabled=False):
+            x = x.to(dt)
+            if "w_in" in w:
+                x = _step_linear(x, w["w_in"], w["b_in"], w["frame"])
+            x = _step_linear(x, w["w_emb"], w["b_emb"], w["frame"])
+            pending = None
+            for i, blk in enumerate(self.blocks):
+                bw = w["blocks"][i]
+                if pending is None:
+                    n = blk.norm_mlstm(x)
+                else:
+                    x, n = _add_norm(x, pending, blk.norm_mlstm)
+                y = blk.mlstm_layer.step(n, state[i], live, bw["mlstm"])
+                x, n = _add_norm(x, y, blk.norm_ffn)
+                pending = blk.ffn.step(n, bw["ffn"])
+            if pending is None:
+                h = self.out_norm(x)
+            else:
+                x, h = _add_norm(x, pending, self.out_norm)
+            logits = soft_cap(_step_linear(h, w["w_lm"], w["b_lm"], w["frame"]),
+                              self.config.output_logit_soft_cap)
+        return logits, state
+
+    def _forward_inference(self, x, state):
+        """mode="inference" (the xlstm package's wrap_chunkwise_arbitrary_sequence_length): the
+        first T - T % 64 frames on the chunkwise path, the remainder on the step path from the
+        state the chunks leave; T < 64 is all step path.  The caller's state is not modified."""
+        if torch.is_grad_enabled() and (x.requires_grad or
+                                        any(p.requires_grad for p in self.parameters())):
+            raise RuntimeError('xLSTMLarge(mode="inference") has no backward (the recurrent step '
+                               'kernel is forward only): run it under torch.no_grad(), or use '
+                               'mode="train" with T % 64 == 0')
+        B, T, _ = x.shape
+        T0 = T - T % self.config.chunk_size
+        parts = []
+        if T0:
+            logits, state = self._forward_train(x[:, :T0], state)
+            parts.append(logits)
+        if T0 < T or not parts:
+            zero = self.zero_state(B, x.device)
+            state = {i: tuple((zero[i][j] if state is None or state.get(i) is None
+                               or state[i][j] is None else
+                               state[i][j].detach().to(x.device, torch.float32).clone()
+                               ).contiguous().view(zero[i][j].shape) for j in range(3))
+                     for i in zero}
+            logits, state = self.step(x[:, T0:], state)
+            parts.append(logits if not parts else logits.to(parts[0].dtype))
+        logits = parts[0] if len(parts) == 1 else torch.cat(parts, 1)
+        return (logits, state) if self.config.return_last_states else logits
+
     def forward(self, x, state=None):
+        if self.config.mode == "inference":
+            return self._forward_inference(x, state)
+        out = self._forward_train(x, state)
+        return out if self.config.return_last_states else out[0]
+
+    def _forward_train(self, x, state=None):
         x = self.embedding(x)
         new_state = {}
         # xLSTMBlock.forward unrolled so that every residual add meets the RMSNorm reading its
@@ -305,6 +534,4 @@ class xLSTMLarge(nn.Module):
         else:
             x, h = _add_norm(x, pending, self.out_norm)
         logits = soft_cap(self.lm_head(h), self.config.output_logit_soft_cap)
-        if self.config.return_last_states:
-            return logits, new_state
-        return logits
+        return logits, new_state
