@@ -42,6 +42,9 @@
  *                        n-best with scores, offline and chunked
  *   sc_ctc_align      <- (absent in the reference; its README plans hallucination filtering) CTC
  *                        forced alignment: Viterbi path, token spans, per-frame / per-token scores
+ *   sc_wkv_*          <- (planned in the reference's README, absent from its code) the RWKV-4 WKV
+ *                        operator with carried state, math as transformers/models/rwkv/
+ *                        modeling_rwkv.py `rwkv_linear_attention_cpu`
  */
 #ifndef STATECATCHER_H
 #define STATECATCHER_H
@@ -1162,6 +1165,40 @@ int sc_rnnt_beam_frames(const void* enc_p, const void* pred_tab, const void* W, 
 int sc_rnnt_beam_result(const void* state, size_t state_bytes, int B, int beam, int max_symbols,
                         int nbest, int32_t* tokens, int32_t* frames, int cap, int32_t* lens,
                         float* scores, int32_t* status, void* stream);
+
+/* ---- RWKV-4 WKV operator --------------------------------------------------------------------
+ * Per batch row b and channel c, with W = -exp(time_decay[c]), u = time_first[c] and the state
+ * S = (A, B) held as (num, den, max), A = num e^max, B = den e^max, for t = 0 .. T-1:
+ *     y_t     = (A_t + e^{u+k_t} v_t) / (B_t + e^{u+k_t})
+ *     S_{t+1} = e^W S_t + e^{k_t} (v_t, 1)
+ * evaluated with running maxima (transformers' rwkv_linear_attention_cpu), so no exponential
+ * overflows.  k, v, y (and dy, dk, dv) are contiguous [B,T,C] of one dtype, SC_F32 or SC_BF16;
+ * time_decay, time_first, their gradients, the state and all arithmetic are fp32.
+ *   forward   num_in / den_in / max_in fp32 [B,C], all three or all null: the incoming state (null:
+ *             the empty state num = den = 0, max = -1e38, which may also be passed explicitly).
+ *             num_out / den_out / max_out <- the state after T steps (T == 0: the incoming one).
+ *             They may alias the incoming arrays.  ckpt: null, or fp32 of
+ *             sc_wkv_ckpt_numel(B, T, C) elements <- the state at the start of every super-chunk of
+ *             sc_wkv_chunk() steps, which is all the backward needs besides its inputs.
+ *   backward  dy = dL/dy; the incoming state is a constant and the outgoing state carries no
+ *             gradient.  dk, dv <- the input gradients, d_time_decay / d_time_first fp32 [C] <-
+ *             the parameter gradients summed over rows and steps in a fixed order (no atomics:
+ *             two runs are bitwise equal; B == 0 or T == 0 gives zeros).  ws: fp32 scratch of
+ *             sc_wkv_bwd_ws_numel(B, T, C) elements.
+ * Any B, T, C >= 0 (B <= 65535); B == 0 or C == 0 launch nothing in the forward.  The size
+ * functions return 0 for negative arguments.  No host sync, no allocation.
+ */
+int sc_wkv_chunk(void);
+int64_t sc_wkv_ckpt_numel(int B, int T, int C);
+int64_t sc_wkv_bwd_ws_numel(int B, int T, int C);
+int sc_wkv_fwd(const float* time_decay, const float* time_first, const void* k, const void* v,
+               int dtype, const float* num_in, const float* den_in, const float* max_in, void* y,
+               float* num_out, float* den_out, float* max_out, float* ckpt, int B, int T, int C,
+               void* stream);
+int sc_wkv_bwd(const float* time_decay, const float* time_first, const void* k, const void* v,
+               const void* dy, int dtype, const float* ckpt, void* dk, void* dv,
+               float* d_time_decay, float* d_time_first, float* ws, int B, int T, int C,
+               void* stream);
 
 #ifdef __cplusplus
 }

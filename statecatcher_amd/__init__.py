@@ -8,11 +8,13 @@ from .lucyrnn_conf import LucyRNNConfig
 from .lucyrnn_triton import LinearSafe, LucyRNNCellTriton, LucyRNNtriton
 from .lucyrnn import LucyRNN, LucyRNNCell
 from .xlstm import xLSTMLarge, xLSTMLargeConfig
+from .rwkv import RWKVConfig, RWKVEncoder
 from .model import (ASRModel, CTCLoss, RNNTCompactPredictorJoiner, RNNTLoss, RNNTPredictorJoiner,
-                    build_lucyrnn_config, build_xlstm_config, compute_loss, detach_states)
+                    build_lucyrnn_config, build_rwkv_config, build_xlstm_config, compute_loss,
+                    detach_states)
 from .ops import (ctc_align, ctc_beam_decode, ctc_beam_result, ctc_beam_state, ctc_greedy_decode,
                   ctc_loss, ctc_nll, decay_scan, lucy_scan, mlstm_chunkwise, rnnt_beam_decode,
-                  rnnt_beam_result, rnnt_beam_state, rnnt_greedy_decode, rnnt_loss)
+                  rnnt_beam_result, rnnt_beam_state, rnnt_greedy_decode, rnnt_loss, wkv)
 from .decoder import (ctc_beam_decoder, ctc_forced_align, ctc_greedy_decoder, rnnt_beam_decoder,
                       rnnt_greedy_decoder)
 from .streaming import StreamingLucyRNN, StreamingLucyRNNtriton, StreamingXLSTM
@@ -26,5 +28,5 @@ __all__ = [
     "StreamingLucyRNN", "StreamingLucyRNNtriton", "StreamingXLSTM", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
     "ctc_beam_decode", "ctc_beam_state", "ctc_beam_result", "ctc_beam_decoder",
     "rnnt_beam_decode", "rnnt_beam_state", "rnnt_beam_result", "rnnt_beam_decoder",
-    "ctc_align", "ctc_forced_align",
+    "ctc_align", "ctc_forced_align", "RWKVConfig", "RWKVEncoder", "build_rwkv_config", "wkv",
 ]

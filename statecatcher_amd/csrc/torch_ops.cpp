@@ -23,6 +23,7 @@
 //   ctc_beam_*      (absent in the reference: decoder.py is greedy only) CTC prefix beam search
 //   rnnt_beam_*     (absent in the reference) transducer beam search of RNNTPredictorJoiner
 //   ctc_align       (absent in the reference) CTC forced alignment: path, token spans, scores
+//   wkv_fwd/_bwd    (planned in the reference's README) the RWKV-4 WKV operator with carried state
 // There is no CPU kernel: calling an op on CPU tensors raises (no silent fallback).
 
 #include <ATen/ATen.h>
@@ -1163,6 +1164,100 @@ Tensor clip_adam_meta(at::TensorList params, at::TensorList grads, at::TensorLis
   return at::empty({}, params[0].options());
 }
 
+// ------------------------------------------------------------------------ RWKV-4 WKV ----------
+std::tuple<int64_t, int64_t, int64_t> wkv_dims(const Tensor& td, const Tensor& tf, const Tensor& k,
+                                               const Tensor& v) {
+  TORCH_CHECK(k.dim() == 3 && k.sizes() == v.sizes(),
+              "statecatcher::wkv: k / v must be equal [B,T,C]; got ", k.sizes(), ", ", v.sizes());
+  TORCH_CHECK(k.scalar_type() == v.scalar_type() &&
+                  (k.scalar_type() == at::kFloat || k.scalar_type() == at::kBFloat16),
+              "statecatcher::wkv: k / v must share float32 or bfloat16; got ", k.scalar_type(), ", ",
+              v.scalar_type());
+  const int64_t C = k.size(2);
+  TORCH_CHECK(td.dim() == 1 && td.size(0) == C && tf.dim() == 1 && tf.size(0) == C,
+              "statecatcher::wkv: time_decay / time_first must be [C]=[", C, "]");
+  return {k.size(0), k.size(1), C};
+}
+
+bool wkv_state(const optional<Tensor>& n, const optional<Tensor>& d, const optional<Tensor>& m,
+               int64_t B, int64_t C) {
+  const bool has = n && n->defined();
+  TORCH_CHECK(has == (d && d->defined()) && has == (m && m->defined()),
+              "statecatcher::wkv_fwd: the state is num, den and max together, or none of them");
+  for (const auto* s : {&n, &d, &m})
+    TORCH_CHECK(!has || (*s)->sizes() == at::IntArrayRef({B, C}),
+                "statecatcher::wkv_fwd: state tensors must be [B,C]=[", B, ",", C, "]");
+  return has;
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> wkv_fwd_hip(
+    const Tensor& td_in, const Tensor& tf_in, const Tensor& k_in, const Tensor& v_in,
+    const optional<Tensor>& num0, const optional<Tensor>& den0, const optional<Tensor>& max0,
+    bool need_ckpt) {
+  c10::DeviceGuard guard(k_in.device());
+  auto [B, T, C] = wkv_dims(td_in, tf_in, k_in, v_in);
+  const bool has = wkv_state(num0, den0, max0, B, C);
+  Tensor td = f32c(td_in), tf = f32c(tf_in), k = k_in.contiguous(), v = v_in.contiguous();
+  Tensor n0, d0, m0;
+  if (has) n0 = f32c(*num0), d0 = f32c(*den0), m0 = f32c(*max0);
+  auto fo = k.options().dtype(at::kFloat);
+  Tensor y = at::empty_like(k);
+  Tensor num = at::empty({B, C}, fo), den = at::empty({B, C}, fo), mx = at::empty({B, C}, fo);
+  Tensor ckpt = at::empty({need_ckpt ? sc_wkv_ckpt_numel(B, T, C) : 0}, fo);
+  sc_check(sc_wkv_fwd(td.data_ptr<float>(), tf.data_ptr<float>(), k.data_ptr(), v.data_ptr(),
+                      dtype_code(k), has ? n0.data_ptr<float>() : nullptr,
+                      has ? d0.data_ptr<float>() : nullptr, has ? m0.data_ptr<float>() : nullptr,
+                      y.data_ptr(), num.data_ptr<float>(), den.data_ptr<float>(),
+                      mx.data_ptr<float>(), need_ckpt ? ckpt.data_ptr<float>() : nullptr, B, T, C,
+                      stream_for(k)),
+           "statecatcher::wkv_fwd");
+  return {y, num, den, mx, ckpt};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> wkv_fwd_meta(
+    const Tensor& td, const Tensor& tf, const Tensor& k, const Tensor& v,
+    const optional<Tensor>& num0, const optional<Tensor>& den0, const optional<Tensor>& max0,
+    bool need_ckpt) {
+  auto [B, T, C] = wkv_dims(td, tf, k, v);
+  wkv_state(num0, den0, max0, B, C);
+  auto fo = k.options().dtype(at::kFloat);
+  return {at::empty(k.sizes(), k.options()), at::empty({B, C}, fo), at::empty({B, C}, fo),
+          at::empty({B, C}, fo), at::empty({need_ckpt ? sc_wkv_ckpt_numel(B, T, C) : 0}, fo)};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> wkv_bwd_hip(const Tensor& td_in, const Tensor& tf_in,
+                                                       const Tensor& k_in, const Tensor& v_in,
+                                                       const Tensor& dy_in, const Tensor& ckpt) {
+  c10::DeviceGuard guard(k_in.device());
+  auto [B, T, C] = wkv_dims(td_in, tf_in, k_in, v_in);
+  TORCH_CHECK(dy_in.sizes() == k_in.sizes(), "statecatcher::wkv_bwd: dy must be [B,T,C]");
+  TORCH_CHECK(ckpt.numel() == sc_wkv_ckpt_numel(B, T, C) && ckpt.scalar_type() == at::kFloat,
+              "statecatcher::wkv_bwd: ckpt is not the forward's checkpoint (run the forward with "
+              "need_ckpt=True)");
+  Tensor td = f32c(td_in), tf = f32c(tf_in), k = k_in.contiguous(), v = v_in.contiguous();
+  Tensor dy = dy_in.to(k.scalar_type()).contiguous();
+  auto fo = k.options().dtype(at::kFloat);
+  Tensor dk = at::empty_like(k), dv = at::empty_like(v);
+  Tensor dtd = at::empty({C}, fo), dtf = at::empty({C}, fo);
+  Tensor ws = at::empty({sc_wkv_bwd_ws_numel(B, T, C)}, fo);
+  sc_check(sc_wkv_bwd(td.data_ptr<float>(), tf.data_ptr<float>(), k.data_ptr(), v.data_ptr(),
+                      dy.data_ptr(), dtype_code(k), ckpt.data_ptr<float>(), dk.data_ptr(),
+                      dv.data_ptr(), dtd.data_ptr<float>(), dtf.data_ptr<float>(),
+                      ws.data_ptr<float>(), B, T, C, stream_for(k)),
+           "statecatcher::wkv_bwd");
+  return {dtd, dtf, dk, dv};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> wkv_bwd_meta(const Tensor& td, const Tensor& tf,
+                                                        const Tensor& k, const Tensor& v,
+                                                        const Tensor& dy, const Tensor& ckpt) {
+  auto [B, T, C] = wkv_dims(td, tf, k, v);
+  TORCH_CHECK(dy.sizes() == k.sizes(), "statecatcher::wkv_bwd: dy must be [B,T,C]");
+  auto fo = k.options().dtype(at::kFloat);
+  return {at::empty({C}, fo), at::empty({C}, fo), at::empty(k.sizes(), k.options()),
+          at::empty(v.sizes(), v.options())};
+}
+
 }  // namespace
 
 
@@ -1234,6 +1329,11 @@ TORCH_LIBRARY(statecatcher, m) {
         "Tensor? lengths=None, Tensor? mask=None, int blank=0, int beam=8, int top_k=8, "
         "int max_symbols=2, int nbest=1, int? max_frames=None, int? cap=None)"
         " -> (Tensor tokens, Tensor lens, Tensor scores, Tensor frames)");
+  m.def("wkv_fwd(Tensor time_decay, Tensor time_first, Tensor k, Tensor v, Tensor? num0=None, "
+        "Tensor? den0=None, Tensor? max0=None, bool need_ckpt=True)"
+        " -> (Tensor y, Tensor num, Tensor den, Tensor max, Tensor ckpt)");
+  m.def("wkv_bwd(Tensor time_decay, Tensor time_first, Tensor k, Tensor v, Tensor dy, Tensor ckpt)"
+        " -> (Tensor d_time_decay, Tensor d_time_first, Tensor dk, Tensor dv)");
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
@@ -1265,6 +1365,8 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("rnnt_beam_frames_", &rnnt_beam_frames_hip);
   m.impl("rnnt_beam_result", &rnnt_beam_result_hip);
   m.impl("rnnt_beam_decode", &rnnt_beam_decode_hip);
+  m.impl("wkv_fwd", &wkv_fwd_hip);
+  m.impl("wkv_bwd", &wkv_bwd_hip);
 }
 
 TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
@@ -1296,4 +1398,6 @@ TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("rnnt_beam_frames_", &rnnt_beam_frames_meta);
   m.impl("rnnt_beam_result", &rnnt_beam_result_meta);
   m.impl("rnnt_beam_decode", &rnnt_beam_decode_meta);
+  m.impl("wkv_fwd", &wkv_fwd_meta);
+  m.impl("wkv_bwd", &wkv_bwd_meta);
 }

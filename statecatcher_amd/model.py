@@ -14,6 +14,7 @@ import torch.nn as nn
 from .lucyrnn_conf import LucyRNNConfig
 from .lucyrnn_triton import DEFERRED_LOGITS, LucyRNNtriton, defer_output_head
 from .xlstm import xLSTMLarge, xLSTMLargeConfig
+from .rwkv import RWKVConfig, RWKVEncoder
 from .ops import ctc_head_loss, ctc_head_supported, ctc_loss, rnnt_joint_loss, rnnt_joint_supported, rnnt_loss
 
 
@@ -271,6 +272,14 @@ class ASRModel(nn.Module):
             self.input_seq_pad_factor = 8
             if proj_dim > 0:
                 self.proj = nn.Linear(feat_dim, proj_dim)
+        elif isinstance(encoder, RWKVConfig):
+            # (the reference's README plans an RWKV encoder; its model.py builds none)
+            self.cfg = encoder
+            self.encoder = RWKVEncoder(self.cfg)
+            self.enc_out_dim = vocab_size
+            self.input_seq_pad_factor = 1   # any T: no time padding
+            if proj_dim > 0:
+                self.proj = nn.Linear(feat_dim, proj_dim)
         else:
             raise ValueError(f"Unknown encoder provided: {type(encoder)}")
 
@@ -315,3 +324,10 @@ def build_lucyrnn_config(input_dim, hidden_size, num_layers, vocab_size, is_trai
     return LucyRNNConfig(input_dim=input_dim, hidden_dim=hidden_size, num_layers=num_layers,
                          vocab_size=vocab_size, return_last_states=True, kernel_impl="triton",
                          fused_ops=True, stack_order=1, layer_norm=False, is_training=is_training)
+
+
+def build_rwkv_config(feat_dim, vocab_size, hidden_size, num_layers):
+    """The RWKV-4 encoder config in the builders' style (attention width = hidden_size,
+    intermediate = 4 * hidden_size: the published RWKV-4 proportions)."""
+    return RWKVConfig(input_dim=feat_dim, hidden_size=hidden_size, num_layers=num_layers,
+                      vocab_size=vocab_size, return_last_states=True)

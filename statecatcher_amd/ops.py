@@ -818,6 +818,90 @@ def decay_scan(kv, decay, init=None):
     return DecayScanFn.apply(kv, decay, init)
 
 
+# ----------------------------------------------------------------------------- RWKV-4 WKV ----
+WKV_CHUNK = 64   # steps per super-chunk of csrc/wkv.hip (sc_wkv_chunk): one checkpoint each
+
+
+def _wkv_check(time_decay, time_first, k, v, state):
+    """(B, T, C) of valid WKV operands; raises otherwise."""
+    if k.dim() != 3 or k.shape != v.shape:
+        raise ValueError(f"wkv: k / v must be equal [B,T,C]; got {tuple(k.shape)}, {tuple(v.shape)}")
+    if k.dtype != v.dtype or k.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"wkv: k / v must share fp32 or bf16, got {k.dtype}, {v.dtype}")
+    B, T, C = k.shape
+    if tuple(time_decay.shape) != (C,) or tuple(time_first.shape) != (C,):
+        raise ValueError(f"wkv: time_decay / time_first must be [C]=({C},); got "
+                         f"{tuple(time_decay.shape)}, {tuple(time_first.shape)}")
+    if state is not None:
+        if len(state) != 3 or any(tuple(s.shape) != (B, C) for s in state):
+            raise ValueError(f"wkv: state must be (num, den, max), each [B,C]=({B},{C})")
+        if any(s.requires_grad for s in state):
+            raise ValueError("wkv: the incoming state is a constant (detach it: the segment loop "
+                             "does); it must not require grad")
+    return B, T, C
+
+
+class WKVFn(torch.autograd.Function):
+    """(y, num, den, max) of the RWKV-4 WKV operator (csrc/wkv.hip) from the state (num0, den0,
+    max0), all None for the empty state.  Differentiable in time_decay, time_first, k and v; the
+    outgoing state carries no gradient."""
+
+    @staticmethod
+    def forward(ctx, time_decay, time_first, k, v, num0, den0, max0):
+        require_device(time_decay, time_first, k, v, num0, den0, max0)
+        B, T, C = k.shape
+        td = time_decay.detach().float().contiguous()
+        tf = time_first.detach().float().contiguous()
+        kc, vc = k.contiguous(), v.contiguous()
+        st = [None if s is None else s.detach().float().contiguous() for s in (num0, den0, max0)]
+        y = torch.empty_like(kc)
+        num, den, mx = (torch.empty(B, C, dtype=torch.float32, device=k.device) for _ in range(3))
+        lib = _lib.load()
+        need = any(ctx.needs_input_grad[:4])
+        ckpt = None
+        if need:
+            ckpt = torch.empty(lib.sc_wkv_ckpt_numel(B, T, C), dtype=torch.float32, device=k.device)
+        e = kc.element_size()
+        with _timed("wkv_fwd", kc, 3 * B * T * C * e + (ckpt.numel() * 4 if need else 0)):
+            rc = lib.sc_wkv_fwd(ptr(td), ptr(tf), ptr(kc), ptr(vc), dtype_code(kc), ptr(st[0]),
+                                ptr(st[1]), ptr(st[2]), ptr(y), ptr(num), ptr(den), ptr(mx),
+                                ptr(ckpt), B, T, C, stream_of(kc))
+        check(rc, "sc_wkv_fwd")
+        if need:
+            ctx.save_for_backward(td, tf, kc, vc, ckpt)
+            ctx.pdt = (time_decay.dtype, time_first.dtype)
+        ctx.mark_non_differentiable(num, den, mx)
+        return y, num, den, mx
+
+    @staticmethod
+    def backward(ctx, dy, _dnum, _dden, _dmax):
+        td, tf, kc, vc, ckpt = ctx.saved_tensors
+        B, T, C = kc.shape
+        dy = dy.to(kc.dtype).contiguous()
+        dk, dv = torch.empty_like(kc), torch.empty_like(vc)
+        dtd, dtf = (torch.empty(C, dtype=torch.float32, device=kc.device) for _ in range(2))
+        lib = _lib.load()
+        ws = torch.empty(lib.sc_wkv_bwd_ws_numel(B, T, C), dtype=torch.float32, device=kc.device)
+        e = kc.element_size()
+        with _timed("wkv_bwd", kc, 5 * B * T * C * e + ckpt.numel() * 4):
+            rc = lib.sc_wkv_bwd(ptr(td), ptr(tf), ptr(kc), ptr(vc), ptr(dy), dtype_code(kc),
+                                ptr(ckpt), ptr(dk), ptr(dv), ptr(dtd), ptr(dtf), ptr(ws), B, T, C,
+                                stream_of(kc))
+        check(rc, "sc_wkv_bwd")
+        return dtd.to(ctx.pdt[0]), dtf.to(ctx.pdt[1]), dk, dv, None, None, None
+
+
+def wkv(time_decay, time_first, k, v, state=None):
+    """The RWKV-4 WKV operator: (y [B,T,C] in k's dtype, (num, den, max) fp32 [B,C] each), the state
+    after the T frames.  k, v fp32 or bf16; time_decay, time_first [C]; state = (num, den, max) of
+    an earlier call, or None for the empty state.  Any T >= 0: feeding a sequence in pieces with the
+    state carried equals feeding it whole."""
+    require_device(time_decay, time_first, k, v, *(state or ()))
+    _wkv_check(time_decay, time_first, k, v, state)
+    y, num, den, mx = WKVFn.apply(time_decay, time_first, k, v, *(state or (None, None, None)))
+    return y, (num, den, mx)
+
+
 # ----------------------------------------------------------------------------- CTC -----------
 def _as_len_tensor(x, device):
     if isinstance(x, torch.Tensor):

@@ -24,6 +24,7 @@ Reference interfaces (what a ``train.py`` user swaps in):
   ctc_beam_decode <- (absent in the reference: decoder.py is greedy only) CTC prefix beam search
   rnnt_beam_decode <- (absent in the reference) transducer beam search of RNNTPredictorJoiner
   ctc_align   <- (absent in the reference) CTC forced alignment: path, token spans, scores
+  wkv         <- (planned in the reference's README) the RWKV-4 WKV operator with carried state
 """
 import os
 
@@ -36,7 +37,7 @@ OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay
        "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode", "ctc_beam_state_bytes",
        "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode",
        "rnnt_beam_state_bytes", "rnnt_beam_reset_", "rnnt_beam_frames_", "rnnt_beam_result",
-       "rnnt_beam_decode", "ctc_align")
+       "rnnt_beam_decode", "ctc_align", "wkv_fwd", "wkv_bwd")
 
 _LOADED = False
 
@@ -186,6 +187,21 @@ def _joint_backward(ctx, grad_nll, grad_ws):
     return de.to(ed), dp.to(pd), dW.to(wd), db.to(bd), None, None, None, None
 
 
+def _wkv_setup(ctx, inputs, output):
+    td, tf, k, v = inputs[:4]
+    ctx.save_for_backward(td, tf, k, v, output[4])
+    ctx.pdt = (td.dtype, tf.dtype)
+
+
+def _wkv_backward(ctx, dy, dnum, dden, dmax, dckpt):
+    """Gradients of y alone: the incoming state is a constant and the outgoing one carries none."""
+    td, tf, k, v, ckpt = ctx.saved_tensors
+    if dy is None:
+        dy = torch.zeros_like(k)
+    dtd, dtf, dk, dv = torch.ops.statecatcher.wkv_bwd(td, tf, k, v, dy, ckpt)
+    return dtd.to(ctx.pdt[0]), dtf.to(ctx.pdt[1]), dk, dv, None, None, None, None
+
+
 def _register_autograd():
     reg = torch.library.register_autograd
     reg("statecatcher::lucy_scan_fwd", _scan_backward, setup_context=_scan_setup)
@@ -195,6 +211,7 @@ def _register_autograd():
     reg("statecatcher::ctc_mean", _mean_backward, setup_context=_mean_setup)
     reg("statecatcher::mlstm_fwd", _mlstm_backward, setup_context=_mlstm_setup)
     reg("statecatcher::rnnt_joint_fwd", _joint_backward, setup_context=_joint_setup)
+    reg("statecatcher::wkv_fwd", _wkv_backward, setup_context=_wkv_setup)
 
 
 # ------------------------------------------------------------------------------- functions ----
@@ -243,6 +260,19 @@ def mlstm(q, k, v, igate, fgate, c0=None, n0=None, m0=None, eps=1e-6):
     h, c_last, ns, ms, _, _, _ = load().mlstm_fwd(q, k, v, igate, fgate, c0, n0, m0, eps)
     B, NH = q.shape[:2]
     return h, (c_last, ns[:, -1].reshape(B, NH, -1), ms[:, -1].reshape(B, NH, 1))
+
+
+def wkv(time_decay, time_first, k, v, state=None):
+    """(y [B,T,C], (num, den, max) fp32 [B,C]) of the RWKV-4 WKV operator (ops.wkv) from the state
+    (num, den, max), or the empty state.  Differentiable in time_decay, time_first, k and v; the
+    state is a constant going in and carries no gradient coming out."""
+    sc = load()
+    if state is not None and any(s.requires_grad for s in state):
+        raise ValueError("wkv: the incoming state is a constant (detach it); it must not require grad")
+    need = torch.is_grad_enabled() and any(t.requires_grad for t in (time_decay, time_first, k, v))
+    n0, d0, m0 = state if state is not None else (None, None, None)
+    y, num, den, mx, _ = sc.wkv_fwd(time_decay, time_first, k, v, n0, d0, m0, need)
+    return y, (num.detach(), den.detach(), mx.detach())
 
 
 def rnnt_joint_nll(enc_p, pred_p, W, bias, labels, frames_lengths, labels_lengths, blank=0):
