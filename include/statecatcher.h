@@ -45,6 +45,8 @@
  *   sc_wkv_*          <- (planned in the reference's README, absent from its code) the RWKV-4 WKV
  *                        operator with carried state, math as transformers/models/rwkv/
  *                        modeling_rwkv.py `rwkv_linear_attention_cpu`
+ *   sc_wkv_step, sc_rwkv_step_mix, sc_relu_sq <- the same model one frame at a time (RwkvBlock,
+ *                        RwkvSelfAttention, RwkvFeedForward at T = 1) for streaming decode
  */
 #ifndef STATECATCHER_H
 #define STATECATCHER_H
@@ -1199,6 +1201,53 @@ int sc_wkv_bwd(const float* time_decay, const float* time_first, const void* k, 
                const void* dy, int dtype, const float* ckpt, void* dk, void* dv,
                float* d_time_decay, float* d_time_first, float* ws, int B, int T, int C,
                void* stream);
+
+/* ---- RWKV-4 streaming step (csrc/rwkv_step.hip) ---------------------------------------------
+ * What a block of K frames of B concurrent streams needs besides its GEMMs.  Activations are
+ * [K][B][width] with explicit frame and row strides in elements (unit inner stride), SC_F32 or
+ * SC_BF16; the state and all arithmetic are fp32.  live: fp32 [K][B] contiguous, or null (every
+ * frame live); a frame with live == 0 is HELD: it leaves the state bitwise untouched.  A frame's
+ * arithmetic does not depend on K or on its position in the call: K frames in one call equal K
+ * calls of one frame bitwise.  No host sync, no allocation: safe inside a hipGraph capture.
+ *
+ *   sc_wkv_step       the recurrence of sc_wkv_fwd, one step at a time in its order, for K steps:
+ *                     (num, den, max) fp32 [B,C] are read once, advanced IN PLACE and written
+ *                     once (never null: the empty state is num = den = 0, max = -1e38, passed
+ *                     explicitly).  k, v [K][B][C] share stride_t / stride_b; r: null, or the
+ *                     receptance pre-activation in the same layout, and then y <- sigmoid(r) y.
+ *                     y [K][B][C] in the operand dtype with its own strides; a held step writes a
+ *                     zero row.  Any C >= 1, B <= 65535; K, B or C == 0 launch nothing.
+ *   sc_rwkv_step_mix  per stream, in frame order, on the residual row h (fp32 [K][B][H], IN PLACE):
+ *                       h += add, or h += sigmoid(gate) * add   (add / gate [K][B][H] in io_dtype,
+ *                                                                sharing add_stride_*; either null)
+ *                       h = LayerNorm(h; pre_w, pre_b)          (pre_w / pre_b null: skipped)
+ *                       a = LayerNorm(h; ln_w, ln_b)            (fp32 two-pass statistics, eps)
+ *                       s = the a of the stream's last live frame before this one, x_prev[b] for
+ *                           its first live frame
+ *                       out_i = a * mix_i + s * (1 - mix_i),  i < nmix    (mix_i fp32 [H])
+ *                       nmix == 0: out_0 = a
+ *                       live: x_prev[b] = a
+ *                     h is rewritten when an add or pre_ln is given.  out_i [K][B][H] in io_dtype
+ *                     share out_stride_*.  x_prev fp32 [B,H] IN PLACE; a stream with no live
+ *                     frame leaves its row bitwise untouched; null only with nmix == 0 (nothing
+ *                     is carried then).  The output rows of held frames are finite and not
+ *                     meaningful.  1 <= H <= 2048, nmix in [0, 3]; K or B == 0 launch nothing.
+ *   sc_relu_sq        x <- max(x, 0)^2 in place over n contiguous elements (the feed-forward's
+ *                     squared ReLU); n == 0 launches nothing.
+ * All return SC_EINVAL with sc_last_error() naming the argument for a dtype other than fp32 /
+ * bf16, a shape outside the limits, a null state or a required pointer that is null.
+ */
+int sc_wkv_step(const float* time_decay, const float* time_first, const void* k, const void* v,
+                const void* r, int dtype, int64_t stride_t, int64_t stride_b, const float* live,
+                float* num, float* den, float* max, void* y, int64_t y_stride_t,
+                int64_t y_stride_b, int K, int B, int C, void* stream);
+int sc_rwkv_step_mix(float* h, int64_t h_stride_t, int64_t h_stride_b, const void* add,
+                     const void* gate, int64_t add_stride_t, int64_t add_stride_b, int io_dtype,
+                     const float* pre_w, const float* pre_b, const float* ln_w, const float* ln_b,
+                     float eps, float* x_prev, const float* live, int nmix, const float* mix0,
+                     const float* mix1, const float* mix2, void* out0, void* out1, void* out2,
+                     int64_t out_stride_t, int64_t out_stride_b, int K, int B, int H, void* stream);
+int sc_relu_sq(void* x, int dtype, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

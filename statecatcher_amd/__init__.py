@@ -17,7 +17,8 @@ from .ops import (ctc_align, ctc_beam_decode, ctc_beam_result, ctc_beam_state, c
                   rnnt_beam_result, rnnt_beam_state, rnnt_greedy_decode, rnnt_loss, wkv)
 from .decoder import (ctc_beam_decoder, ctc_forced_align, ctc_greedy_decoder, rnnt_beam_decoder,
                       rnnt_greedy_decoder)
-from .streaming import StreamingLucyRNN, StreamingLucyRNNtriton, StreamingXLSTM
+from .streaming import (StreamingLucyRNN, StreamingLucyRNNtriton, StreamingRWKV,
+                        StreamingXLSTM)
 from .frontend import make_frontend
 
 __all__ = [
@@ -25,7 +26,7 @@ __all__ = [
     "compute_loss", "detach_states", "build_lucyrnn_config", "build_xlstm_config", "ctc_greedy_decode", "ctc_loss", "ctc_nll", "decay_scan",
     "lucy_scan", "ctc_greedy_decoder", "rnnt_loss", "RNNTLoss", "RNNTPredictorJoiner",
     "RNNTCompactPredictorJoiner", "xLSTMLarge", "xLSTMLargeConfig", "mlstm_chunkwise",
-    "StreamingLucyRNN", "StreamingLucyRNNtriton", "StreamingXLSTM", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
+    "StreamingLucyRNN", "StreamingLucyRNNtriton", "StreamingXLSTM", "StreamingRWKV", "make_frontend", "rnnt_greedy_decode", "rnnt_greedy_decoder",
     "ctc_beam_decode", "ctc_beam_state", "ctc_beam_result", "ctc_beam_decoder",
     "rnnt_beam_decode", "rnnt_beam_state", "rnnt_beam_result", "rnnt_beam_decoder",
     "ctc_align", "ctc_forced_align", "RWKVConfig", "RWKVEncoder", "build_rwkv_config", "wkv",

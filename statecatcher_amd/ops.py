@@ -902,6 +902,153 @@ def wkv(time_decay, time_first, k, v, state=None):
     return y, (num, den, mx)
 
 
+# ------------------------------------------------------------------ RWKV-4 streaming step ----
+def _step_state(what, named, shape, dev):
+    """The carried state of a step op: fp32, contiguous, on the operands' device.  It is updated in
+    place, so nothing is cast or copied here: a wrong dtype or layout raises (as _mlstm_step_state)."""
+    for name, t in named:
+        if t is None or tuple(t.shape) != shape:
+            raise ValueError(f"{what}: state {name} has shape "
+                             f"{None if t is None else tuple(t.shape)}, expected {shape}")
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{what}: state {name} must be a contiguous fp32 tensor on {dev} "
+                             "(it is updated in place)")
+
+
+def _step_live(what, live, B, K, dev):
+    """live [B,K] as the step kernels read it: fp32 [K][B] contiguous.  The transposed view of an
+    fp32 [K,B] buffer is taken as it is (no allocation); anything else is converted."""
+    if live is None:
+        return None
+    if tuple(live.shape) != (B, K):
+        raise ValueError(f"{what}: live has shape {tuple(live.shape)}, expected {(B, K)}")
+    lt = live.t()
+    if live.dtype == torch.float32 and live.device == dev and lt.is_contiguous():
+        return lt
+    return lt.to(dev, torch.float32).contiguous()
+
+
+def _step_rows(what, name, t, B, K, W, dtype):
+    """(frame stride, row stride) of an activation [B,K,W] with unit inner stride in ``dtype``."""
+    if tuple(t.shape) != (B, K, W) or t.dtype != dtype or (W > 1 and t.stride(2) != 1):
+        raise ValueError(f"{what}: {name} must be {dtype} [B,K,{W}]=({B},{K},{W}) with unit inner "
+                         f"stride; got {t.dtype} {tuple(t.shape)} strides {t.stride()}")
+    # (a stride that is never multiplied is normalised, so views of one row / one frame compare)
+    return (W if K == 1 else t.stride(1)), (W if B == 1 else t.stride(0))
+
+
+@torch.no_grad()
+def wkv_step(time_decay, time_first, k, v, state, r=None, live=None, out=None):
+    """The recurrent WKV operator (csrc/rwkv_step.hip, sc_wkv_step): k, v [B,K,C] (fp32 or bf16;
+    any batch / frame strides, unit inner stride, both the same) advance the state (num, den, max)
+    fp32 [B,C] IN PLACE by K steps and return y [B,K,C] in k's dtype -- ops.wkv's recurrence one
+    step at a time in its order.  r [B,K,C] (k's layout): y <- sigmoid(r) y.  live [B,K]: steps
+    with 0 hold the state and return a zero row.  out: the y buffer (no allocation then, given
+    fp32 time_decay / time_first and a live mask that is the transpose of an fp32 [K,B] buffer).
+    K steps in one call equal K calls of one step bitwise.  No gradient."""
+    require_device(time_decay, time_first, k, v, r, out, *(state or ()))
+    what = "wkv_step"
+    if k.dim() != 3 or k.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what}: k must be fp32 or bf16 [B,K,C], got {k.dtype} {tuple(k.shape)}")
+    B, K, C = k.shape
+    if tuple(time_decay.shape) != (C,) or tuple(time_first.shape) != (C,):
+        raise ValueError(f"{what}: time_decay / time_first must be [C]=({C},)")
+    if state is None or len(state) != 3:
+        raise ValueError(f"{what}: state must be (num, den, max), each fp32 [B,C] (the empty state "
+                         "is (0, 0, -1e38): RWKVEncoder.zero_state)")
+    _step_state(what, zip(("num", "den", "max"), state), (B, C), k.device)
+    st, sb = _step_rows(what, "k", k, B, K, C, k.dtype)
+    for name, t in (("v", v), ("r", r)):
+        if t is not None and _step_rows(what, name, t, B, K, C, k.dtype) != (st, sb) \
+                and B * K * C > 0:
+            raise ValueError(f"{what}: {name} must have k's strides")
+    y = torch.empty(K, B, C, dtype=k.dtype, device=k.device).transpose(0, 1) if out is None else out
+    yt, yb = _step_rows(what, "out", y, B, K, C, k.dtype)
+    lv = _step_live(what, live, B, K, k.device)
+    td = time_decay.detach().float().contiguous()
+    tf = time_first.detach().float().contiguous()
+    check(_lib.load().sc_wkv_step(ptr(td), ptr(tf), ptr(k), ptr(v), ptr(r), dtype_code(k), st, sb,
+                                  ptr(lv), ptr(state[0]), ptr(state[1]), ptr(state[2]), ptr(y), yt,
+                                  yb, K, B, C, stream_of(k)), "sc_wkv_step")
+    return y
+
+
+@torch.no_grad()
+def rwkv_step_mix(h, ln, x_prev=None, mixes=(), outs=None, add=None, gate=None, pre_ln=None,
+                  live=None, eps=1e-5):
+    """Residual update, LayerNorm(s), time shift and time mixes of K frames of B streams in one
+    launch (csrc/rwkv_step.hip, include/statecatcher.h sc_rwkv_step_mix).  h fp32 [B,K,H] (any
+    batch / frame strides): the residual rows, IN PLACE: h += add or h += sigmoid(gate) * add,
+    then h = pre_ln(h) when given.  a = LayerNorm(h; ln); with 1..3 ``mixes`` (fp32 [H]) out_i =
+    a * m_i + s * (1 - m_i), s the a of the stream's previous live frame (x_prev fp32 [B,H] for
+    the first; x_prev <- the last live a, IN PLACE); with none, out_0 = a.  ln / pre_ln: (weight,
+    bias) fp32 [H].  add / gate / outs share one dtype (fp32 or bf16) and, among themselves, their
+    strides.  live [B,K]: frames with 0 leave x_prev alone (their output rows are not
+    meaningful).  outs: the output buffers (allocated when None).  Returns the list of outputs.
+    No allocation when outs is given and live is the transpose of an fp32 [K,B] buffer."""
+    what = "rwkv_step_mix"
+    require_device(h, x_prev, add, gate, *ln, *(pre_ln or ()), *mixes, *(outs or ()))
+    if h.dim() != 3 or h.dtype != torch.float32:
+        raise TypeError(f"{what}: h must be fp32 [B,K,H], got {h.dtype} {tuple(h.shape)}")
+    B, K, H = h.shape
+    nmix = len(mixes)
+    if nmix > 3:
+        raise ValueError(f"{what}: at most 3 mixes, got {nmix}")
+    ht, hb = _step_rows(what, "h", h, B, K, H, torch.float32)
+    if x_prev is None:
+        if nmix:
+            raise ValueError(f"{what}: the mixes need x_prev (the carried shift frame)")
+    else:
+        _step_state(what, (("x_prev", x_prev),), (B, H), h.device)
+    for name, p in (("ln", ln), ("pre_ln", pre_ln), ("mixes", mixes)):
+        for t in p or ():
+            if t.dtype != torch.float32 or t.numel() != H or not t.is_contiguous():
+                raise ValueError(f"{what}: {name} parameters must be contiguous fp32 [{H}]")
+    io = add if add is not None else (outs[0] if outs else None)
+    iod = io.dtype if io is not None else torch.float32
+    if iod not in (torch.float32, torch.bfloat16):
+        raise TypeError(f"{what}: add / gate / outs must be fp32 or bf16, got {iod}")
+    if gate is not None and add is None:
+        raise ValueError(f"{what}: gate without add")
+    at = ab = 0
+    if add is not None:
+        at, ab = _step_rows(what, "add", add, B, K, H, iod)
+        if gate is not None and _step_rows(what, "gate", gate, B, K, H, iod) != (at, ab) \
+                and B * K > 0:
+            raise ValueError(f"{what}: gate must have add's strides")
+    nout = max(nmix, 1)
+    if outs is None:
+        outs = [torch.empty(K, B, H, dtype=iod, device=h.device).transpose(0, 1)
+                for _ in range(nout)]
+    if len(outs) != nout:
+        raise ValueError(f"{what}: {nout} output buffers expected, got {len(outs)}")
+    ot, ob = _step_rows(what, "out", outs[0], B, K, H, iod)
+    for o in outs[1:]:
+        if _step_rows(what, "out", o, B, K, H, iod) != (ot, ob) and B * K > 0:
+            raise ValueError(f"{what}: the outputs must share their strides")
+    lv = _step_live(what, live, B, K, h.device)
+    pw, pb = pre_ln if pre_ln is not None else (None, None)
+    m = list(mixes) + [None] * (3 - nmix)
+    o = list(outs) + [None] * (3 - nout)
+    check(_lib.load().sc_rwkv_step_mix(
+        ptr(h), ht, hb, ptr(add), ptr(gate), at, ab, _lib._DTYPE[iod], ptr(pw), ptr(pb),
+        ptr(ln[0]), ptr(ln[1]), float(eps), ptr(x_prev), ptr(lv), nmix, ptr(m[0]), ptr(m[1]),
+        ptr(m[2]), ptr(o[0]), ptr(o[1]), ptr(o[2]), ot, ob, K, B, H, stream_of(h)),
+        "sc_rwkv_step_mix")
+    return list(outs)
+
+
+@torch.no_grad()
+def relu_sq_(x):
+    """x <- relu(x)^2 in place (sc_relu_sq: the RWKV feed-forward's squared ReLU); x contiguous
+    fp32 or bf16.  No allocation."""
+    require_device(x)
+    if not x.is_contiguous():
+        raise ValueError("relu_sq_: x must be contiguous (it is updated in place)")
+    check(_lib.load().sc_relu_sq(ptr(x), dtype_code(x), x.numel(), stream_of(x)), "sc_relu_sq")
+    return x
+
+
 # ----------------------------------------------------------------------------- CTC -----------
 def _as_len_tensor(x, device):
     if isinstance(x, torch.Tensor):

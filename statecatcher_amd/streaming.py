@@ -52,6 +52,9 @@ runs) the same way.  Its cell normalises per element, so a layer of a frame is O
 (lucy_tframe_layer: LayerNorm on load, 7-gate projection, cell in the epilogue), a frame L + 2
 launches and a wavefront block (K + L - 1) + 2.  Both classes share the block / capture / tail /
 API code (_StreamBase).
+
+StreamingXLSTM and StreamingRWKV stream the other two encoders on their own step methods
+(xLSTMLarge.step, RWKVEncoder.step) with the same capture, tails and API.
 """
 import torch
 
@@ -733,3 +736,102 @@ class StreamingXLSTM(_StreamBase):
     def state(self):
         """{block: (C, n, m)} fp32 copies: xLSTMLarge.forward's ``state``."""
         return {i: tuple(t.clone() for t in st) for i, st in self.states.items()}
+
+
+class StreamingRWKV(_StreamBase):
+    """Decode ``batch`` concurrent streams through an RWKVEncoder (rwkv.py; weights snapshotted
+    at construction) ``frames_per_call`` frames per call.
+
+    A block is RWKVEncoder.step on static buffers (its step_workspace): per RWKV block the
+    shift-mix kernel (residual, LayerNorm, time shift and the mixes of the block's K frames in one
+    launch), the k / v / r GEMMs as one multi-job launch, ONE recurrent WKV launch (csrc/
+    rwkv_step.hip: (num, den, max) read once, held in registers over the K steps, written once,
+    in place; the receptance gate in its epilogue), the output GEMM, the second shift-mix, the
+    feed-forward's two GEMM launches and its squared ReLU: 8 launches per block of the stack for
+    the K frames; then the final LayerNorm, the output projection and the greedy CTC / transducer
+    tail of the other streamers.  A linear chain on one stream, captured once as a hipGraph.
+
+    dtype: the weight dtype of the GEMMs.  State: RWKVEncoder.forward's (x_att, x_ffn, num, den,
+    max), each fp32 [L,B,C]: reset(state) and state() hand over between an offline segment and
+    the stream in both directions.  Frames with mask 0 hold every block's state (both shift
+    frames and the WKV triple, bitwise) and emit nothing -- where the offline forward on zero
+    padding pushes the padding into the WKV state and overwrites the shift frames.
+    input_proj: an nn.Linear applied before the encoder's own input projection (an ASRModel's
+    ``proj``).
+    gemm: "frame" runs the linears on lucy_frame_gemm (csrc/lucy_frame.hip: fp32 activations,
+    arithmetic per row independent of the block size, so a block of K frames equals K calls of
+    one frame bitwise).  "library" runs the library GEMM in ``dtype`` with activations in
+    ``dtype`` (it picks its kernel by the row count, so block sizes agree to rounding only).
+    "auto": "frame" where its limits hold (every reduction length -- input_dim, H, A, I and
+    input_proj's width -- a multiple of 8 and <= 2048), else "library".
+    """
+
+    engine = "frame"     # (the transducer tail's enc_proj runs on lucy_frame_gemm)
+    schedule = "frame"
+
+    def __init__(self, model, batch: int, frames_per_call: int = 1, dtype=torch.bfloat16,
+                 graph: bool = True, blank: int = 0, joiner=None, max_symbols: int = 4, beam=None,
+                 top_k: int = 8, nbest: int = 1, max_frames: int = 4096, input_proj=None,
+                 gemm: str = "auto"):
+        import copy
+
+        from .rwkv import RWKVEncoder
+        if not isinstance(model, RWKVEncoder):
+            raise TypeError(f"StreamingRWKV streams an RWKVEncoder, got {type(model).__name__}")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("streaming: weights fp32 or bf16")
+        cfg = model.config
+        dev = next(model.parameters()).device
+        ops._lib.require_device(next(model.parameters()))
+        self.cfg, self.B, self.K, self.dtype, self.blank = cfg, batch, frames_per_call, dtype, blank
+        self.L, self.V = cfg.num_layers, cfg.vocab_size
+        B, K = batch, frames_per_call
+        # the snapshot: a private copy of the module and every weight cast once
+        self.model = copy.deepcopy(model).eval().requires_grad_(False)
+        self.weights = self.model.step_weights(dtype, input_proj, gemm)
+        self.gemm = self.weights["gemm"]
+        self.joiner = joiner is not None
+        if beam is not None and not self.joiner:
+            raise ValueError("beam= needs a joiner (the beam search is the transducer's)")
+        if self.joiner:
+            self._init_joiner(joiner, max_symbols, dev, beam, top_k, nbest, max_frames)
+        self.ws = self.model.step_workspace(B, K, self.weights, dev)
+        self.x, self.mask, self.logits = self.ws["x"], self.ws["live"], self.ws["logits"]
+        self.Din = self.x.shape[2]
+        self.states = self.model.zero_state(B, dev)
+        self.emit = torch.full((K, B), -1, dtype=torch.int32, device=dev)
+        self.prev = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        if self.joiner:
+            self.enc_p = torch.zeros(K, B, self.J, dtype=torch.float32, device=dev)
+        self.graph = None
+        if graph:
+            self._capture()
+        self.reset()
+
+    def _block(self):
+        self.model._step_block(self.ws, self.states, self.mask, self.weights)
+        if self.joiner:
+            return self._rnnt_block()
+        ops.ctc_greedy_frames(self.logits, self.prev, self.emit, mask=self.mask, blank=self.blank)
+
+    # ------------------------------------------------------------------------------- API ---
+    def reset(self, state=None, streams=None):
+        """Start streams afresh: state from ``state`` ((x_att, x_ffn, num, den, max), each
+        [L,B,C]: what RWKVEncoder.forward returns and takes) or the state before the first frame
+        (zero shift frames, the empty WKV state), prev token = none (``blank`` with a joiner).
+        ``streams``: the streams to reset (default all)."""
+        idx = slice(None) if streams is None else torch.as_tensor(streams, device=self.x.device)
+        if state is not None and len(state) != 5:
+            raise ValueError("StreamingRWKV.reset: state must be (x_att, x_ffn, num, den, max)")
+        zero = self.model.zero_state(self.B, self.x.device) if state is None else None
+        for i, buf in enumerate(self.states):
+            src = zero[i] if state is None else \
+                state[i].detach().to(buf.device, torch.float32).reshape(buf.shape)
+            buf[:, idx] = src[:, idx]
+        self.prev[idx] = self.blank if self.joiner else -1
+        if self.beam is not None:
+            self.beam_state.reset(None if streams is None else torch.as_tensor(streams).tolist())
+
+    def state(self):
+        """(x_att, x_ffn, num, den, max) fp32 copies: RWKVEncoder.forward's ``state``."""
+        return tuple(t.clone() for t in self.states)
