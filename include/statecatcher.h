@@ -211,6 +211,40 @@ int sc_lucy_scan_bwd_ln(const void* gates, int gates_dtype, const float* gate_bi
                         int64_t stride_dg_cb, const float* ln_r, const float* ln_stat,
                         void* stream);
 
+/*
+ * The masked scan: sc_lucy_scan_fwd / sc_lucy_scan_fwd_split with a per-frame mask.
+ *   mask   uint8 [B,T] contiguous, nonzero = live.  NULL is SC_EINVAL (callers without a mask
+ *          use sc_lucy_scan_fwd).
+ * A held frame (mask == 0) leaves (h, s) untouched and writes zero to out (and to out_dup /
+ * out_lo); its gates are never used (selects, not products: they may hold NaN).  So a row's
+ * result is the unmasked scan over its live frames, scattered back; s_out / h_out are the state
+ * after the last live frame, and a row with no live frame returns (h0, s0).  h_out is therefore
+ * not out[:, T-1].  out_dup / out_lo: both NULL, or the split planes (16-bit gates).  ckpt keeps
+ * sc_lucy_scan_fwd's layout.  The LayerNorm-fold variants have no masked form.
+ */
+int sc_lucy_scan_fwd_masked(const void* gates, int gates_dtype, const float* gate_bias,
+                            const float* h0, const float* s0, const uint8_t* mask, void* out,
+                            void* out_dup, void* out_lo, float* s_out, float* h_out, int B, int T,
+                            int D, int64_t stride_g_bt, int64_t stride_g_td, int64_t stride_g_cd,
+                            int64_t stride_g_cb, int64_t stride_o_bt, int64_t stride_o_bd,
+                            float* ckpt, void* stream);
+
+/*
+ * Backward of sc_lucy_scan_fwd_masked (same mask).  A held frame gets exactly zero in all 7 gate
+ * planes of dgates and adds nothing to dbias; neither its gates nor its dout are used.
+ *   dh_last  fp32 [B,D] = dL/d h_out, NULL = zero: the initial value of the Gh chain, the way
+ *            ds_last starts Gs (it reaches the last LIVE step; it is not added onto dout[:, T-1]).
+ * A row with no live frame returns dh0 = dh_last, ds0 = ds_last.
+ */
+int sc_lucy_scan_bwd_masked(const void* gates, int gates_dtype, const float* gate_bias,
+                            const float* ckpt, const void* dout, const float* ds_last,
+                            const float* dh_last, const uint8_t* mask, void* dgates, float* dh0,
+                            float* ds0, float* dbias, int B, int T, int D, int64_t stride_g_bt,
+                            int64_t stride_g_td, int64_t stride_g_cd, int64_t stride_g_cb,
+                            int64_t stride_d_bt, int64_t stride_d_bd, int64_t stride_dg_bt,
+                            int64_t stride_dg_td, int64_t stride_dg_cd, int64_t stride_dg_cb,
+                            void* stream);
+
 /* ---------------------------------------------------------------- decay scan ------------ */
 
 /*

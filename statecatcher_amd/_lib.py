@@ -21,7 +21,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "statecatcher.h")
 _SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
             "float": ctypes.c_float, "double": ctypes.c_double}
 _RETURNS = dict(_SCALARS, **{"void": None, "const char *": ctypes.c_char_p})
-_POINTEES = set(_SCALARS) | {"void", "char", "int32_t"}   # and the header's own structs
+_POINTEES = set(_SCALARS) | {"void", "char", "int32_t", "uint8_t"}   # and the header's own structs
 _STRUCT = re.compile(r"typedef\s+struct\s*(\w*)\s*\{([^{}]*)\}\s*(\w+)\s*;")
 _PROTO = re.compile(r"(\w[\w\s*]*?)\b(\w+)\s*\(([^(){};]*)\)\s*;")
 _DEFINE = re.compile(r"^[ \t]*#[ \t]*define[ \t]+(SC_\w+)\b(.*)$", re.M)

@@ -86,6 +86,9 @@ struct ScanFwdArgs {
   float2* ln_stat;
   float2* rec_out;
   float ln_eps;
+  // masked scan (sc_lucy_scan_fwd_masked): uint8 [B,T], nonzero = live; a held step leaves
+  // (h, s) untouched and stores zero.  Read by the MASK instances only.
+  const uint8_t* mask;
 };
 
 struct ScanBwdArgs {
@@ -105,6 +108,10 @@ struct ScanBwdArgs {
   // (what the projection's input and weight gradients consume); dbias stays dL/dg
   const float* ln_r;
   const float2* ln_stat;
+  // masked scan (sc_lucy_scan_bwd_masked): the forward's mask, and dL/d h_last (fp32 [B,D], NULL =
+  // zero), the initial value of the Gh chain.  Read by the MASK instances only.
+  const uint8_t* mask;
+  const float* dh_last;
 };
 
 // LDS-DMA piece geometry: a 64-unit row of T elements is PPR pieces of PW bytes.  A partial
@@ -309,6 +316,27 @@ __device__ __forceinline__ float compose_suffix(const float2 (*agg)[64], int lan
   return x;
 }
 
+// ------------------------------------------------------------------------ mask word --------
+// The masked scans (MASK instances): a held step (mask[b,t] == 0) is the identity step the
+// guarded body already applies past the end of the sequence, so a per-frame mask only widens that
+// predicate.  Every wave loads the super-chunk's 64 mask bytes with lane = step (zero past T) and
+// ballots them into a 64-bit live word, bit j = step j of the super-chunk.  All waves read the
+// same bytes, so the word is uniform over the workgroup and may steer the choice between the FULL
+// and the guarded body, barriers included.  The byte of the next super-chunk is loaded one
+// super-chunk ahead and balloted after the wait that retires the gate DMA anyway.
+// The load is unconditional, at a step clamped into the row (T >= 1), and its result is first
+// looked at in live_word: a branch around the load, or a compare scheduled up to it, takes the
+// load's vmcnt(0) along and drains the gate DMA just issued (measured: +16..21% on both kernels).
+__device__ __forceinline__ uint32_t mask_byte(const uint8_t* row, int k, int lane, int T) {
+  return (uint32_t)row[max(min(k * kChunk + lane, T - 1), 0)];
+}
+__device__ __forceinline__ uint64_t live_word(uint32_t byte, int k, int lane, int T) {
+  asm volatile("" : "+v"(byte));   // (pins the first use here, behind the DMA wait)
+  const uint64_t v = __ballot(byte != 0u && (unsigned)(k * kChunk + lane) < (unsigned)T);
+  return ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+         (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+}
+
 // ------------------------------------------------------------------------ forward ----------
 // Reductions over aligned groups of N lanes (N = 2, 4, 8, 16) through DPP: every lane of a group
 // ends with the group's sum.
@@ -326,10 +354,12 @@ __device__ __forceinline__ float group_sum_dpp(float x) {
 // LayerNorm, ScanFwdArgs::ln_r): bit 1 = this layer's gates are u = h W''^T of the previous raw
 // output (combine its block records, rebuild the gates on load); bit 2 = write this output's
 // block records.  NB = D / 64 column blocks per row (LN only).
-template <int DT, int NW, int LC, int PW, int FD, bool SPLIT = false, int LN = 0, int NB = 8>
+template <int DT, int NW, int LC, int PW, int FD, bool SPLIT = false, int LN = 0, int NB = 8,
+          bool MASK = false>
 __global__ void __launch_bounds__(NW * 64)
 lucy_scan_fwd_kernel(ScanFwdArgs a) {
   static_assert(NW * LC == kChunk, "super-chunk must be 64 steps");
+  static_assert(!MASK || (LN == 0 && FD == 1), "the masked scan: no LayerNorm fold, one slot");
   using E = Elem<DT>;
   using T = typename E::T;
   using P = Pieces<T, PW>;
@@ -438,10 +468,17 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
   };
   if (a.nsc > 0) issue(0);
   if (FD == 2 && a.nsc > 1) issue(1);
+  // (MASK) live: the live word of the super-chunk about to run; mbyte: the next one's byte
+  const uint8_t* mrow = MASK ? a.mask + (int64_t)b * a.T : nullptr;
+  uint32_t mbyte = 0;
+  uint64_t live = ~0ull;
+  if constexpr (MASK) mbyte = a.nsc > 0 ? mask_byte(mrow, 0, lane, a.T) : 0u;
   wait_next(-1);
+  if constexpr (MASK) live = live_word(mbyte, 0, lane, a.T);
   lds_barrier();
   // One super-chunk.  FULL: every step inside the sequence and every lane inside D (no
   // per-step conditions); the tail super-chunk and a partial column block take the guarded one.
+  // (MASK) so does a super-chunk with a held step: held is the guarded body's identity step.
   auto chunk = [&](int k, auto fullc) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(fullc)::value;
     constexpr int LP = LC / 2;
@@ -476,6 +513,9 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
     }
     lds_read_wait();              // slot consumed: it may be refilled with super-chunk k+FD
     if (k + FD < a.nsc) issue_next(k + FD);
+    // (MASK) this wave's LC bits of the live word (steps past T are zero bits: held)
+    const uint32_t lv = MASK ? (uint32_t)(live >> (w * LC)) : ~0u;
+    if constexpr (MASK) mbyte = mask_byte(mrow, k + 1, lane, a.T);
 #pragma unroll
     for (int p = 0; p < LP; ++p) {   // two steps per packed instruction
       const int j = 2 * p;
@@ -486,7 +526,8 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
       if constexpr (!FULL) {
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
-          if (t0 + j + h2 >= a.T) {   // identity step past the end of the sequence
+          // identity step past the end of the sequence (MASK: and at a held step)
+          if (MASK ? !((lv >> (j + h2)) & 1u) : t0 + j + h2 >= a.T) {
             zg[p][h2] = 1.0f; dec[p][h2] = 1.0f; u[p][h2] = 0.0f; x[p][h2] = 0.0f;
           }
         }
@@ -535,6 +576,8 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
     // late wait: super-chunk k+1 has landed in this wave's slot, retired before this
     // super-chunk's own stores (a store issued before a full vmcnt wait would be drained with it)
     wait_next(k);
+    // (the next super-chunk's; lv keeps this one's)
+    if constexpr (MASK) live = live_word(mbyte, k + 1, lane, a.T);
     if (w == 0 && a.ckpt && dok) {
       a.ckpt[((int64_t)(b * a.nsc + k) * 2) * a.D + d] = s_in;
       a.ckpt[((int64_t)(b * a.nsc + k) * 2 + 1) * a.D + d] = h_in;
@@ -542,11 +585,13 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
 #pragma unroll
     for (int j = 0; j < LC; ++j)
       if (FULL || (dok && t0 + j < a.T)) {
-        const T hi = E::st(hs[j]);
+        // (MASK) a held step stores zero in every plane
+        const bool held = MASK && !FULL && !((lv >> j) & 1u);
+        const T hi = E::st(held ? 0.0f : hs[j]);
         obuf.st(hi, vo, (uint32_t)(t0 + j) * otd);
         if constexpr (SPLIT) {
           dbuf.st(hi, vo, (uint32_t)(t0 + j) * otd);
-          lbuf.st(E::st(hs[j] - E::ld(hi)), vo, (uint32_t)(t0 + j) * otd);
+          lbuf.st(E::st(held ? 0.0f : hs[j] - E::ld(hi)), vo, (uint32_t)(t0 + j) * otd);
         }
       }
     if constexpr ((LN & 2) != 0) {
@@ -583,7 +628,7 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
   };
   const bool blk_full = (blk + 1) * 64 <= a.D;
   for (int k = 0; k < a.nsc; ++k) {
-    if (blk_full && (k + 1) * kChunk <= a.T)
+    if (blk_full && (k + 1) * kChunk <= a.T && (!MASK || live == ~0ull))
       chunk(k, std::true_type{});
     else
       chunk(k, std::false_type{});
@@ -606,10 +651,11 @@ lucy_scan_fwd_kernel(ScanFwdArgs a) {
 // u = h W''^T, rebuilt as rstd (u - mean r) + b' on load; 2 (ln_r NULL): the projection GEMM has
 // already applied the fold (sc_gemm_tn_ln_bf16 wrote rstd (u - mean r)), the gates take b' alone.
 // Both store d/du = rstd dL/dgate.
-template <int DT, int NW, int LC, int PW, int NBUF, bool WST, int LN = 0>
+template <int DT, int NW, int LC, int PW, int NBUF, bool WST, int LN = 0, bool MASK = false>
 __global__ void __launch_bounds__(NW * 64)
 lucy_scan_bwd_kernel(ScanBwdArgs a) {
   static_assert(NW * LC == kChunk, "super-chunk must be 64 steps");
+  static_assert(!MASK || LN == 0, "the masked scan: no LayerNorm fold");
   using E = Elem<DT>;
   using T = typename E::T;
   using P = Pieces<T, PW>;
@@ -648,7 +694,9 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
   const Buf<T> dgbuf((T*)a.dgates + (int64_t)b * a.dg_bt + (int64_t)blk * a.dg_cb);
   const uint32_t vo = (uint32_t)lane * sizeof(T);
   if (w == 0) {
-    carGh[0][lane] = 0.0f;
+    // (MASK) dL/d h_last starts the Gh chain the way ds_last starts Gs: it reaches the last
+    // live step through the identity steps of the held tail
+    carGh[0][lane] = (MASK && a.dh_last && dok) ? a.dh_last[(int64_t)b * a.D + d] : 0.0f;
     carGs[0][lane] = (a.ds_last && dok) ? a.ds_last[(int64_t)b * a.D + d] : 0.0f;
   }
   float gb[LN ? 1 : 7];
@@ -759,11 +807,19 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     bacc1[g] = 0.0f;
   }
   if (a.nsc > 0) issue(0);
+  // (MASK) live: the live word of the super-chunk about to run; mbyte: the next one's byte
+  const uint8_t* mrow = MASK ? a.mask + (int64_t)b * a.T : nullptr;
+  uint32_t mbyte = 0;
+  uint64_t live = ~0ull;
+  if constexpr (MASK) mbyte = a.nsc > 0 ? mask_byte(mrow, a.nsc - 1, lane, a.T) : 0u;
   dma_wait();
+  if constexpr (MASK) live = live_word(mbyte, a.nsc - 1, lane, a.T);
   lds_barrier();
   // One super-chunk.  FULL: every step is inside the sequence and every lane inside D, so the
   // body carries no per-step conditions (one basic block the scheduler can interleave); the
   // tail super-chunk and a partial column block take the guarded instance.
+  // (MASK) so does a super-chunk with a held step: held is the guarded body's identity step,
+  // and its gate gradients are stored as zero and stay out of the bias sums.
   auto chunk = [&](int it, auto fullc) __attribute__((always_inline)) {
     constexpr bool FULL = decltype(fullc)::value;
     constexpr int LP = LC / 2;   // step pairs: per-step values live as packed (even, odd) pairs
@@ -771,6 +827,9 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     const int t0 = k * kChunk + w * LC;
     unsigned char* slot = slots + (it % NBUF) * ROWS * 64 * L::BYTES;
     if (NBUF == 2 && it + 1 < a.nsc) issue_next(it + 1);     // into the other slot
+    // (MASK) this wave's LC bits of the live word (steps past T are zero bits: held)
+    const uint32_t lv = MASK ? (uint32_t)(live >> (w * LC)) : ~0u;
+    if constexpr (MASK && NBUF == 2) mbyte = mask_byte(mrow, k - 1, lane, a.T);
     const float s_ck = ckS[it & 1][0][lane];
     const float h_ck = ckS[it & 1][1][lane];
     f2 zg[LP], dec[LP], u[LP], x[LP], dj[LP], sv[LP], hv[LP], wz[LP];
@@ -819,7 +878,8 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
       if constexpr (!FULL) {
 #pragma unroll
         for (int h2 = 0; h2 < 2; ++h2) {
-          if (t0 + j + h2 >= a.T) {   // identity step past the end of the sequence
+          // identity step past the end of the sequence (MASK: and at a held step)
+          if (MASK ? !((lv >> (j + h2)) & 1u) : t0 + j + h2 >= a.T) {
             zg[p][h2] = 1.0f; dec[p][h2] = 1.0f; u[p][h2] = 0.0f; x[p][h2] = 0.0f;
             dj[p][h2] = 0.0f;
           }
@@ -845,6 +905,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     if constexpr (NBUF == 1) {
       lds_read_wait();
       if (it + 1 < a.nsc) issue_next(it + 1);                // refill the slot just read
+      if constexpr (MASK) mbyte = mask_byte(mrow, k - 1, lane, a.T);
     }
     // The Gh adjoint depends only on zg and dout, so its segment map is published with the
     // s map (one barrier); Gs needs c = tanh(hn + s) and goes out with the h map.
@@ -898,6 +959,8 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
     aggB[w][lane] = make_float2(Ah, Bh);
     aggD[w][lane] = make_float2(Ps, Qs);
     dma_wait();                   // the next super-chunk (and its checkpoint) has landed
+    // (the next super-chunk's; lv keeps this one's)
+    if constexpr (MASK) live = live_word(mbyte, k - 1, lane, a.T);
     lds_barrier();                                             // B2
     float h = compose_prefix<NW>(aggB, lane, w, h_ck);
 #pragma unroll
@@ -961,9 +1024,11 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
           const int j = jp + h2;
           if (FULL || (dok && t0 + j < a.T)) {
             const uint32_t so = (uint32_t)((t0 + j) * a.dg_td * sizeof(T));
+            // (MASK) a held step: zero gradient (a select: its gates may hold anything)
+            const bool held = MASK && !FULL && !((lv >> j) & 1u);
 #pragma unroll
             for (int g = 0; g < 7; ++g) {
-              const float og = o[g][h2];
+              const float og = held ? 0.0f : o[g][h2];
               const T ogt = E::st(LN ? og * lrs[h2] : og);
               if constexpr (WST) ((T*)slot)[(j * 7 + g) * 64 + lane] = ogt;   // over its raw gate
               else dgbuf.st(ogt, vo, so + (uint32_t)(g * a.dg_cd * sizeof(T)));
@@ -1004,7 +1069,7 @@ lucy_scan_bwd_kernel(ScanBwdArgs a) {
   for (int it = 0; it < a.nsc; ++it) {
     // (NBUF = 1 keeps 56 raw gates in VGPRs: the freer schedule of the FULL body would spill)
     if constexpr (NBUF == 2) {
-      if (blk_full && (a.nsc - it) * kChunk <= a.T) {
+      if (blk_full && (a.nsc - it) * kChunk <= a.T && (!MASK || live == ~0ull)) {
         chunk(it, std::true_type{});
         continue;
       }
@@ -1045,11 +1110,11 @@ static bool set_lds_limit(K kernel, size_t bytes) {
                              (int)bytes) == hipSuccess;
 }
 
-template <int DT, int PW, bool SPLIT = false, int LN = 0, int NB = 8>
+template <int DT, int PW, bool SPLIT = false, int LN = 0, int NB = 8, bool MASK = false>
 static void launch_fwd(const ScanFwdArgs& a, hipStream_t st) {
   using T = typename Elem<DT>::T;
   constexpr int FD = 1;   // one LDS slot per wave
-  auto kern = lucy_scan_fwd_kernel<DT, kNW, kLC, PW, FD, SPLIT, LN, NB>;
+  auto kern = lucy_scan_fwd_kernel<DT, kNW, kLC, PW, FD, SPLIT, LN, NB, MASK>;
   const size_t lds = (size_t)FD * kNW * kLC * 7 * 64 * LdsElem<T, PW>::BYTES;
   static const bool lds_ok = set_lds_limit(kern, lds);
   (void)lds_ok;
@@ -1057,12 +1122,12 @@ static void launch_fwd(const ScanFwdArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(kern, grid, dim3(kNW * 64), lds, st, a);
 }
 
-template <int DT, int PW, bool WST, int LN = 0>
+template <int DT, int PW, bool WST, int LN = 0, bool MASK = false>
 static void launch_bwd(const ScanBwdArgs& a, hipStream_t st) {
   using T = typename Elem<DT>::T;
   // two slots per wave fit only for 2-byte LDS elements (160 KiB per CU)
   constexpr int NBUF = LdsElem<T, PW>::BYTES == 2 ? 2 : 1;
-  auto kern = lucy_scan_bwd_kernel<DT, kBNW, kBLC, PW, NBUF, WST, LN>;
+  auto kern = lucy_scan_bwd_kernel<DT, kBNW, kBLC, PW, NBUF, WST, LN, MASK>;
   const size_t lds = (size_t)NBUF * kBNW * kBLC * 8 * 64 * LdsElem<T, PW>::BYTES;
   static const bool lds_ok = set_lds_limit(kern, lds);
   (void)lds_ok;
@@ -1099,6 +1164,18 @@ template <int DT>
 static void dispatch_fwd(const ScanFwdArgs& a, hipStream_t st) {
   constexpr int es = (int)sizeof(typename Elem<DT>::T);
   const bool wide = wide_pieces(a.gates, es, a.D, {a.g_bt, a.g_td, a.g_cd, a.g_cb});
+  if (a.mask) {   // the masked instances (scan_fwd refused the LayerNorm fold)
+    if constexpr (es == 2) {
+      if (a.out_lo) {
+        if (wide) launch_fwd<DT, 16, true, 0, 8, true>(a, st);
+        else launch_fwd<DT, es, true, 0, 8, true>(a, st);
+        return;
+      }
+    }
+    if (wide) launch_fwd<DT, 16, false, 0, 8, true>(a, st);
+    else launch_fwd<DT, es, false, 0, 8, true>(a, st);
+    return;
+  }
   if constexpr (es == 2) {
     const int mode = (a.ln_r ? 1 : 0) | (a.rec_out ? 2 : 0);
     if (mode) {   // (scan_fwd checked wide pieces and D)
@@ -1126,9 +1203,17 @@ static void dispatch_bwd(const ScanBwdArgs& a, hipStream_t st) {
       return;
     }
   }
-  if (wide_pieces(a.gates, es, a.D, {a.g_bt, a.g_td, a.g_cd, a.g_cb}) &&
-      wide_pieces(a.dout, es, a.D, {a.d_bt, a.d_bd})) {
-    if (es == 2 && wide_pieces(a.dgates, es, a.D, {a.dg_bt, a.dg_td, a.dg_cd, a.dg_cb}))
+  const bool wide = wide_pieces(a.gates, es, a.D, {a.g_bt, a.g_td, a.g_cd, a.g_cb}) &&
+                    wide_pieces(a.dout, es, a.D, {a.d_bt, a.d_bd});
+  const bool staged = es == 2 && wide_pieces(a.dgates, es, a.D, {a.dg_bt, a.dg_td, a.dg_cd, a.dg_cb});
+  if (a.mask) {   // the masked instances, chosen as the plain ones below
+    if (wide && staged) launch_bwd<DT, 16, es == 2, 0, true>(a, st);
+    else if (wide) launch_bwd<DT, 16, false, 0, true>(a, st);
+    else launch_bwd<DT, es, false, 0, true>(a, st);
+    return;
+  }
+  if (wide) {
+    if (staged)
       launch_bwd<DT, 16, es == 2>(a, st);
     else
       launch_bwd<DT, 16, false>(a, st);
@@ -1162,7 +1247,8 @@ static int scan_fwd(const void* gates, int gates_dtype, const float* gate_bias, 
                     const float* s0, void* out, float* s_out, float* h_out, int B, int T, int D,
                     int64_t stride_g_bt, int64_t stride_g_td, int64_t stride_g_cd,
                     int64_t stride_g_cb, int64_t stride_o_bt, int64_t stride_o_bd, float* ckpt,
-                    void* out_dup, void* out_lo, void* stream, const LnFold& ln = LnFold{}) {
+                    void* out_dup, void* out_lo, void* stream, const LnFold& ln = LnFold{},
+                    const uint8_t* mask = nullptr) {
   SC_REQUIRE(check_dtype(gates_dtype), "sc_lucy_scan_fwd: unsupported gates dtype %d", gates_dtype);
   SC_REQUIRE(B >= 0 && T >= 0 && D >= 0, "sc_lucy_scan_fwd: negative shape B=%d T=%d D=%d", B, T, D);
   SC_REQUIRE(B <= 65535, "sc_lucy_scan_fwd: B=%d exceeds grid limit 65535", B);
@@ -1186,7 +1272,7 @@ static int scan_fwd(const void* gates, int gates_dtype, const float* gate_bias, 
   ScanFwdArgs a{gates, gate_bias, h0, s0, out, s_out, h_out, ckpt, B, T, D, (T + kChunk - 1) / kChunk,
                 stride_g_bt, stride_g_td, stride_g_cd, stride_g_cb, stride_o_bt, stride_o_bd,
                 out_dup, out_lo, ln.r, (const float2*)ln.rec_in, (float2*)ln.stat,
-                (float2*)ln.rec_out, ln.eps};
+                (float2*)ln.rec_out, ln.eps, mask};
   hipStream_t st = (hipStream_t)stream;
   switch (gates_dtype) {
     case SC_F32: dispatch_fwd<SC_F32>(a, st); break;
@@ -1225,6 +1311,24 @@ extern "C" int sc_lucy_scan_fwd_split(const void* gates, int gates_dtype, const 
                   out_lo, stream);
 }
 
+extern "C" int sc_lucy_scan_fwd_masked(const void* gates, int gates_dtype, const float* gate_bias,
+                                       const float* h0, const float* s0, const uint8_t* mask,
+                                       void* out, void* out_dup, void* out_lo, float* s_out,
+                                       float* h_out, int B, int T, int D, int64_t stride_g_bt,
+                                       int64_t stride_g_td, int64_t stride_g_cd,
+                                       int64_t stride_g_cb, int64_t stride_o_bt,
+                                       int64_t stride_o_bd, float* ckpt, void* stream) {
+  clear_error();
+  SC_REQUIRE(mask, "sc_lucy_scan_fwd_masked: null mask (sc_lucy_scan_fwd is the unmasked scan)");
+  SC_REQUIRE((out_dup == nullptr) == (out_lo == nullptr),
+             "sc_lucy_scan_fwd_masked: out_dup and out_lo come together");
+  SC_REQUIRE(!out_lo || gates_dtype == SC_BF16 || gates_dtype == SC_F16,
+             "sc_lucy_scan_fwd_masked: the split planes need a 16-bit out (dtype %d)", gates_dtype);
+  return scan_fwd(gates, gates_dtype, gate_bias, h0, s0, out, s_out, h_out, B, T, D, stride_g_bt,
+                  stride_g_td, stride_g_cd, stride_g_cb, stride_o_bt, stride_o_bd, ckpt, out_dup,
+                  out_lo, stream, LnFold{}, mask);
+}
+
 extern "C" int sc_lucy_scan_fwd_ln(const void* gates, int gates_dtype, const float* gate_bias,
                                    const float* h0, const float* s0, void* out, void* out_dup,
                                    void* out_lo, float* s_out, float* h_out, int B, int T, int D,
@@ -1252,7 +1356,8 @@ static int scan_bwd(const void* gates, int gates_dtype, const float* gate_bias, 
                     int64_t stride_g_cd, int64_t stride_g_cb, int64_t stride_d_bt,
                     int64_t stride_d_bd, int64_t stride_dg_bt, int64_t stride_dg_td,
                     int64_t stride_dg_cd, int64_t stride_dg_cb, const float* ln_r,
-                    const float* ln_stat, void* stream);
+                    const float* ln_stat, void* stream, const uint8_t* mask = nullptr,
+                    const float* dh_last = nullptr);
 
 extern "C" int sc_lucy_scan_bwd(const void* gates, int gates_dtype, const float* gate_bias,
                                 const float* ckpt,
@@ -1267,6 +1372,23 @@ extern "C" int sc_lucy_scan_bwd(const void* gates, int gates_dtype, const float*
                   T, D, stride_g_bt, stride_g_td, stride_g_cd, stride_g_cb, stride_d_bt,
                   stride_d_bd, stride_dg_bt, stride_dg_td, stride_dg_cd, stride_dg_cb, nullptr,
                   nullptr, stream);
+}
+
+extern "C" int sc_lucy_scan_bwd_masked(const void* gates, int gates_dtype, const float* gate_bias,
+                                       const float* ckpt, const void* dout, const float* ds_last,
+                                       const float* dh_last, const uint8_t* mask, void* dgates,
+                                       float* dh0, float* ds0, float* dbias, int B, int T, int D,
+                                       int64_t stride_g_bt, int64_t stride_g_td,
+                                       int64_t stride_g_cd, int64_t stride_g_cb,
+                                       int64_t stride_d_bt, int64_t stride_d_bd,
+                                       int64_t stride_dg_bt, int64_t stride_dg_td,
+                                       int64_t stride_dg_cd, int64_t stride_dg_cb, void* stream) {
+  clear_error();
+  SC_REQUIRE(mask, "sc_lucy_scan_bwd_masked: null mask (sc_lucy_scan_bwd is the unmasked scan)");
+  return scan_bwd(gates, gates_dtype, gate_bias, ckpt, dout, ds_last, dgates, dh0, ds0, dbias, B,
+                  T, D, stride_g_bt, stride_g_td, stride_g_cd, stride_g_cb, stride_d_bt,
+                  stride_d_bd, stride_dg_bt, stride_dg_td, stride_dg_cd, stride_dg_cb, nullptr,
+                  nullptr, stream, mask, dh_last);
 }
 
 extern "C" int sc_lucy_scan_bwd_ln(const void* gates, int gates_dtype, const float* gate_bias,
@@ -1297,7 +1419,8 @@ static int scan_bwd(const void* gates, int gates_dtype, const float* gate_bias, 
                     int64_t stride_g_cd, int64_t stride_g_cb, int64_t stride_d_bt,
                     int64_t stride_d_bd, int64_t stride_dg_bt, int64_t stride_dg_td,
                     int64_t stride_dg_cd, int64_t stride_dg_cb, const float* ln_r,
-                    const float* ln_stat, void* stream) {
+                    const float* ln_stat, void* stream, const uint8_t* mask,
+                    const float* dh_last) {
   SC_REQUIRE(check_dtype(gates_dtype), "sc_lucy_scan_bwd: unsupported gates dtype %d", gates_dtype);
   SC_REQUIRE(B >= 0 && T >= 0 && D >= 0, "sc_lucy_scan_bwd: negative shape B=%d T=%d D=%d", B, T, D);
   SC_REQUIRE(B <= 65535, "sc_lucy_scan_bwd: B=%d exceeds grid limit 65535", B);
@@ -1316,7 +1439,7 @@ static int scan_bwd(const void* gates, int gates_dtype, const float* gate_bias, 
                 (T + kChunk - 1) / kChunk,
                 stride_g_bt, stride_g_td, stride_g_cd, stride_g_cb, stride_d_bt, stride_d_bd,
                 stride_dg_bt, stride_dg_td, stride_dg_cd, stride_dg_cb, ln_r,
-                (const float2*)ln_stat};
+                (const float2*)ln_stat, mask, dh_last};
   hipStream_t st = (hipStream_t)stream;
   switch (gates_dtype) {
     case SC_F32: dispatch_bwd<SC_F32>(a, st); break;

@@ -178,6 +178,106 @@ std::tuple<Tensor, Tensor, Tensor, Tensor> lucy_scan_bwd_meta(const Tensor& gate
           at::empty({want_dbias ? B : 0, 7, D}, fo)};
 }
 
+// ------------------------------------------------------------------------ masked scan ---------
+// (include/statecatcher.h, sc_lucy_scan_fwd_masked: mask [B,T], nonzero = live; any dtype,
+// converted to uint8 on the device)
+Tensor mask_u8(const Tensor& mask, const Tensor& gates, int64_t B, int64_t T, const char* op) {
+  TORCH_CHECK(mask.dim() == 2 && mask.size(0) == B && mask.size(1) == T, op, ": mask must be [B,T]=[",
+              B, ",", T, "], got ", mask.sizes());
+  TORCH_CHECK(mask.device() == gates.device(), op, ": mask is on ", mask.device(), ", gates on ",
+              gates.device());
+  return (mask.scalar_type() == at::kByte ? mask : mask.ne(0).to(at::kByte)).contiguous();
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> lucy_scan_masked_fwd_hip(const Tensor& gates_in,
+                                                                    const Tensor& h0, const Tensor& s0,
+                                                                    const Tensor& mask,
+                                                                    const optional<Tensor>& bias,
+                                                                    bool need_ckpt) {
+  c10::DeviceGuard guard(gates_in.device());
+  Tensor gates = gates_in;
+  if (gates.dim() == 4 && gates.size(2) == 7 && gates.stride(3) != 1) gates = gates.contiguous();
+  const GateLayout L = gate_layout(gates);
+  TORCH_CHECK(h0.sizes() == at::IntArrayRef({L.B, L.D}) && s0.sizes() == at::IntArrayRef({L.B, L.D}),
+              "statecatcher::lucy_scan_masked_fwd: h0/s0 must be [B,D]=[", L.B, ",", L.D, "]");
+  Tensor h0c = f32c(h0), s0c = f32c(s0);
+  Tensor mk = mask_u8(mask, gates, L.B, L.T, "statecatcher::lucy_scan_masked_fwd");
+  optional<Tensor> bc;
+  if (bias && bias->defined()) {
+    TORCH_CHECK(bias->numel() == 7 * L.D,
+                "statecatcher::lucy_scan_masked_fwd: gate_bias must have 7*D elements");
+    bc = f32c(*bias);
+  }
+  auto opt = gates.options();
+  Tensor out = at::empty({L.B, L.T, L.D}, opt);
+  Tensor s_out = at::empty({L.B, L.D}, opt.dtype(at::kFloat));
+  Tensor h_out = at::empty({L.B, L.D}, opt.dtype(at::kFloat));
+  Tensor ckpt = at::empty({need_ckpt ? sc_lucy_scan_ckpt_numel(L.B, L.T, L.D) : 0}, opt.dtype(at::kFloat));
+  sc_check(sc_lucy_scan_fwd_masked(gates.data_ptr(), dtype_code(gates), (const float*)opt_ptr(bc),
+                                   h0c.data_ptr<float>(), s0c.data_ptr<float>(),
+                                   mk.data_ptr<uint8_t>(), out.data_ptr(), nullptr, nullptr,
+                                   s_out.data_ptr<float>(), h_out.data_ptr<float>(), L.B, L.T, L.D,
+                                   L.bt, L.td, L.cd, L.cb, out.stride(0), out.stride(1),
+                                   need_ckpt ? ckpt.data_ptr<float>() : nullptr, stream_for(gates)),
+           "statecatcher::lucy_scan_masked_fwd");
+  return {out, s_out, h_out, ckpt};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> lucy_scan_masked_fwd_meta(const Tensor& gates,
+                                                                     const Tensor& h0, const Tensor& s0,
+                                                                     const Tensor& mask,
+                                                                     const optional<Tensor>& bias,
+                                                                     bool need_ckpt) {
+  return lucy_scan_fwd_meta(gates, h0, s0, bias, need_ckpt);
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> lucy_scan_masked_bwd_hip(
+    const Tensor& gates_in, const Tensor& ckpt, const Tensor& dout_in, const Tensor& mask,
+    const optional<Tensor>& ds_last, const optional<Tensor>& dh_last, const optional<Tensor>& bias,
+    bool want_dbias) {
+  c10::DeviceGuard guard(gates_in.device());
+  Tensor gates = gates_in;
+  if (gates.dim() == 4 && gates.size(2) == 7 && gates.stride(3) != 1) gates = gates.contiguous();
+  const GateLayout L = gate_layout(gates);
+  TORCH_CHECK(ckpt.numel() == sc_lucy_scan_ckpt_numel(L.B, L.T, L.D) && ckpt.scalar_type() == at::kFloat,
+              "statecatcher::lucy_scan_masked_bwd: ckpt is not the forward's checkpoint (run the "
+              "forward with need_ckpt=True)");
+  TORCH_CHECK(dout_in.sizes() == at::IntArrayRef({L.B, L.T, L.D}),
+              "statecatcher::lucy_scan_masked_bwd: dout must be [B,T,D]");
+  Tensor mk = mask_u8(mask, gates, L.B, L.T, "statecatcher::lucy_scan_masked_bwd");
+  Tensor dout = dout_in.to(gates.scalar_type());
+  if (dout.stride(2) != 1) dout = dout.contiguous();
+  optional<Tensor> dsl, dhl, bc;
+  if (ds_last && ds_last->defined()) dsl = f32c(*ds_last);
+  if (dh_last && dh_last->defined()) {
+    TORCH_CHECK(dh_last->sizes() == at::IntArrayRef({L.B, L.D}),
+                "statecatcher::lucy_scan_masked_bwd: dh_last must be [B,D]");
+    dhl = f32c(*dh_last);
+  }
+  if (bias && bias->defined()) bc = f32c(*bias);
+  Tensor dgates = at::empty(gates.sizes(), gates.options().memory_format(at::MemoryFormat::Contiguous));
+  const GateLayout G = gate_layout(dgates);
+  auto fo = gates.options().dtype(at::kFloat);
+  Tensor dh0 = at::empty({L.B, L.D}, fo), ds0 = at::empty({L.B, L.D}, fo);
+  Tensor dbias = at::empty({want_dbias ? L.B : 0, 7, L.D}, fo);
+  sc_check(sc_lucy_scan_bwd_masked(gates.data_ptr(), dtype_code(gates), (const float*)opt_ptr(bc),
+                                   ckpt.data_ptr<float>(), dout.data_ptr(), (const float*)opt_ptr(dsl),
+                                   (const float*)opt_ptr(dhl), mk.data_ptr<uint8_t>(),
+                                   dgates.data_ptr(), dh0.data_ptr<float>(), ds0.data_ptr<float>(),
+                                   want_dbias ? dbias.data_ptr<float>() : nullptr, L.B, L.T, L.D,
+                                   L.bt, L.td, L.cd, L.cb, dout.stride(0), dout.stride(1), G.bt, G.td,
+                                   G.cd, G.cb, stream_for(gates)),
+           "statecatcher::lucy_scan_masked_bwd");
+  return {dgates, dh0, ds0, dbias};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> lucy_scan_masked_bwd_meta(
+    const Tensor& gates, const Tensor& ckpt, const Tensor& dout, const Tensor& mask,
+    const optional<Tensor>& ds_last, const optional<Tensor>& dh_last, const optional<Tensor>& bias,
+    bool want_dbias) {
+  return lucy_scan_bwd_meta(gates, ckpt, dout, ds_last, bias, want_dbias);
+}
+
 // ------------------------------------------------------------------------ decay scan ----------
 void check_kv(const Tensor& kv, const Tensor& decay) {
   TORCH_CHECK(kv.dim() == 3 && kv.sizes() == decay.sizes(),
@@ -1268,6 +1368,11 @@ TORCH_LIBRARY(statecatcher, m) {
   m.def("lucy_scan_bwd(Tensor gates, Tensor ckpt, Tensor dout, Tensor? ds_last=None, "
         "Tensor? gate_bias=None, bool want_dbias=False) -> (Tensor dgates, Tensor dh0, Tensor ds0, "
         "Tensor dbias)");
+  m.def("lucy_scan_masked_fwd(Tensor gates, Tensor h0, Tensor s0, Tensor mask, Tensor? gate_bias=None, "
+        "bool need_ckpt=True) -> (Tensor out, Tensor s_last, Tensor h_last, Tensor ckpt)");
+  m.def("lucy_scan_masked_bwd(Tensor gates, Tensor ckpt, Tensor dout, Tensor mask, Tensor? ds_last=None, "
+        "Tensor? dh_last=None, Tensor? gate_bias=None, bool want_dbias=False) -> (Tensor dgates, "
+        "Tensor dh0, Tensor ds0, Tensor dbias)");
   m.def("decay_scan_fwd(Tensor kv, Tensor decay, Tensor? init=None) -> Tensor");
   m.def("decay_scan_bwd(Tensor decay, Tensor s_all, Tensor dout, Tensor? init=None)"
         " -> (Tensor dkv, Tensor ddecay, Tensor dinit)");
@@ -1339,6 +1444,8 @@ TORCH_LIBRARY(statecatcher, m) {
 TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
   m.impl("lucy_scan_fwd", &lucy_scan_fwd_hip);
   m.impl("lucy_scan_bwd", &lucy_scan_bwd_hip);
+  m.impl("lucy_scan_masked_fwd", &lucy_scan_masked_fwd_hip);
+  m.impl("lucy_scan_masked_bwd", &lucy_scan_masked_bwd_hip);
   m.impl("decay_scan_fwd", &decay_scan_fwd_hip);
   m.impl("decay_scan_bwd", &decay_scan_bwd_hip);
   m.impl("layer_norm_fwd", &layer_norm_fwd_hip);
@@ -1372,6 +1479,8 @@ TORCH_LIBRARY_IMPL(statecatcher, CUDA, m) {
 TORCH_LIBRARY_IMPL(statecatcher, Meta, m) {
   m.impl("lucy_scan_fwd", &lucy_scan_fwd_meta);
   m.impl("lucy_scan_bwd", &lucy_scan_bwd_meta);
+  m.impl("lucy_scan_masked_fwd", &lucy_scan_masked_fwd_meta);
+  m.impl("lucy_scan_masked_bwd", &lucy_scan_masked_bwd_meta);
   m.impl("decay_scan_fwd", &decay_scan_fwd_meta);
   m.impl("decay_scan_bwd", &decay_scan_bwd_meta);
   m.impl("layer_norm_fwd", &layer_norm_fwd_meta);

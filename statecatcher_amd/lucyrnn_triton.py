@@ -21,7 +21,9 @@ import torch.nn as nn
 from .lucyrnn_conf import LucyRNNConfig
 from .ops import (LN_FOLD_MODE, cell_image_spec, colsum, fold_images, layer_norm,
                   layer_norm_supported, ln_fold_ok,
-                  lucy_cell, lucy_cell_ln, proj_dgrad, weight_images, wgrad_splitk)
+                  lucy_cell, lucy_cell_ln, proj_dgrad, scan_mask, weight_images, wgrad_splitk)
+
+MASK_MODES = ("ignore", "hold")
 
 
 class _LinearFn(torch.autograd.Function):
@@ -155,9 +157,10 @@ class LucyRNNCellTriton(nn.Module):
         out, s_out, _ = self.forward_with_h(x, h0, s0)
         return out, s_out
 
-    def forward_with_h(self, x, h0, s0, imgs=None, split_sink=None, rec_sink=None):
+    def forward_with_h(self, x, h0, s0, imgs=None, split_sink=None, rec_sink=None, mask=None):
         """(out, s_out, h_last): h_last = out[:, -1] in fp32, unrounded by a 16-bit out (the
-        state LucyRNNtriton carries).  Projection GEMM + scan are one autograd node: the scan
+        state LucyRNNtriton carries).  mask [B,T] (nonzero = live): the masked scan, whose held
+        frames keep (h, s) and write zero; h_last is then the state after the last live frame.  Projection GEMM + scan are one autograd node: the scan
         backward hands the bias gradient back from registers, the weight gradient runs on the
         MFMA split-L kernel.  imgs: this layer's entry of ops.weight_images (bf16 only);
         split_sink: ops.LucyCellFn's (the scan's split-precision output planes); rec_sink: its
@@ -172,13 +175,19 @@ class LucyRNNCellTriton(nn.Module):
         if imgs is not None and cdt != torch.bfloat16:
             imgs = None
         with torch.autocast("cuda", enabled=False):
-            return lucy_cell(x, w, b, h0, s0, cdt, imgs, split_sink, rec_sink)
+            return lucy_cell(x, w, b, h0, s0, cdt, imgs, split_sink, rec_sink, mask)
 
 
 class LucyRNNtriton(nn.Module):
     """L-layer LucyRNN stack with inter-layer LayerNorm and a vocab projection
     (lucyrnn_triton.py:77-155).  forward(x, hidden_states=None, masks=None) ->
-    (logits, (final_h, final_s)) with final_h/final_s nested [track][layer] of [B, D]."""
+    (logits, (final_h, final_s)) with final_h/final_s nested [track][layer] of [B, D].
+
+    mask_mode (config.mask_mode if present, else "ignore"): "ignore" drops `masks` as the
+    reference does; "hold" hands masks [B,T] (nonzero = live) to every layer's scan, so a masked
+    frame leaves the carried (h, s) untouched, as the streaming classes already treat it.
+    LayerNorm and the output projection are per frame and take no mask: logits at held frames
+    are those of a zero encoder output and are to be ignored."""
 
     def __init__(self, config: LucyRNNConfig):
         super().__init__()
@@ -189,6 +198,9 @@ class LucyRNNtriton(nn.Module):
 
         self.config = config
         self.num_tracks = getattr(config, "num_tracks", 1)
+        self.mask_mode = getattr(config, "mask_mode", "ignore")
+        if self.mask_mode not in MASK_MODES:
+            raise ValueError(f"mask_mode must be one of {MASK_MODES}, got {self.mask_mode!r}")
 
         self.tracks = nn.ModuleList()
         self.norms = nn.ModuleList()
@@ -220,7 +232,16 @@ class LucyRNNtriton(nn.Module):
         else:
             h, s = hidden_states
 
-        cell_imgs, out_imgs, fold = self._weight_images(x)
+        if self.mask_mode not in MASK_MODES:
+            raise ValueError(f"mask_mode must be one of {MASK_MODES}, got {self.mask_mode!r}")
+        mask = None
+        if self.mask_mode == "hold" and masks is not None:
+            if masks.dim() == 3 and masks.shape[-1] == 1:
+                masks = masks[..., 0]
+            mask = scan_mask(masks, B, T, x.device)   # one uint8 copy for every layer
+        # (the LayerNorm-fold scans have no masked variant: hold takes the unfolded path)
+        cell_imgs, out_imgs, fold = (self._weight_images(x) if mask is None else
+                                     self._weight_images_unfolded(x))
         req = getattr(_HEAD, "req", None)
         op = self.output_proj
         if req is not None and not (out_imgs is not None and out_imgs[1] is not None
@@ -255,7 +276,7 @@ class LucyRNNtriton(nn.Module):
                 else:
                     x_t, s_t[l], h_t[l] = layer.forward_with_h(
                         x_t, h_t[l], s_t[l], cell_imgs.get((t, l)) if cell_imgs else None,
-                        sink if last else None, rsink)
+                        sink if last else None, rsink, mask)
                 rec = rsink[0] if rsink else None
                 if l < len(norms) and not fold:
                     x_t = norms[l](x_t)
@@ -330,6 +351,14 @@ class LucyRNNtriton(nn.Module):
             out = (wc, wt, rest[0][0] if rest else None)
         folded = {w: im for w, im in zip(fwhere, fold_images(fspecs))} if fold else None
         return cell, out, folded
+
+    def _weight_images_unfolded(self, x):
+        """_weight_images without the LayerNorm fold, whatever SC_LN_FOLD says (the masked
+        forward: the folded scans have no masked variant)."""
+        if not (x.is_cuda and torch.is_autocast_enabled("cuda")
+                and torch.get_autocast_dtype("cuda") == torch.bfloat16):
+            return None, None, None
+        return self._weight_images_plain(x, torch.is_grad_enabled())
 
     def _weight_images_plain(self, x, grad):
         specs, where = [], []

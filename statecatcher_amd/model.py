@@ -251,11 +251,22 @@ class RNNTCompactPredictorJoiner(nn.Module):
 
 class ASRModel(nn.Module):
     """model.py:282-398, LucyRNN branch: optional input projection, zero-masking of padded
-    frames, encoder call with/without carried state."""
+    frames, encoder call with/without carried state.
+
+    masking: "zero" (the reference: padded frames are zeroed, the recurrence still steps over
+    them) or "hold" (LucyRNN only: the features are zeroed as before and the mask also goes to
+    the encoder, whose scans hold (h, s) at masked frames, so padding does not decay the state
+    carried to the next segment)."""
 
     def __init__(self, frontend: Optional[nn.Module], encoder, vocab_size: int, feat_dim: int,
-                 proj_dim: int, debug: bool = False):
+                 proj_dim: int, debug: bool = False, masking: str = "zero"):
         super().__init__()
+        if masking not in ("zero", "hold"):
+            raise ValueError(f'masking must be "zero" or "hold", got {masking!r}')
+        if masking == "hold" and not isinstance(encoder, LucyRNNConfig):
+            raise NotImplementedError('masking="hold" is implemented for the LucyRNN encoder only '
+                                      f"(got {type(encoder).__name__})")
+        self.masking = masking
         self.frontend = frontend
         self.debug = debug
         if isinstance(encoder, xLSTMLargeConfig):   # model.py:301-307
@@ -268,6 +279,8 @@ class ASRModel(nn.Module):
         elif isinstance(encoder, LucyRNNConfig):
             self.cfg = encoder
             self.encoder = LucyRNNtriton(self.cfg)
+            if masking == "hold":
+                self.encoder.mask_mode = "hold"
             self.enc_out_dim = vocab_size
             self.input_seq_pad_factor = 8
             if proj_dim > 0:
@@ -300,7 +313,9 @@ class ASRModel(nn.Module):
                     mask = torch.nn.functional.pad(mask, (0, pad))
         if mask is not None:
             feats = feats * mask.unsqueeze(-1).to(feats.dtype)
-        if states is not None:
+        if self.masking == "hold" and mask is not None:
+            logits, new_states = self.encoder(feats, states, masks=mask)
+        elif states is not None:
             logits, new_states = self.encoder(feats, states)
         else:
             logits, new_states = self.encoder(feats)

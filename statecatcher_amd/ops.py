@@ -54,15 +54,31 @@ def gate_layout(gates):
                      f"shape {tuple(gates.shape)} strides {gates.stride()}")
 
 
-def _scan_fwd(gates, h0, s0, need_ckpt, bias=None, want_h=False, split=False, ln=None):
+def scan_mask(mask, B, T, device):
+    """A frame mask (bool, integer or float; nonzero = live) as the contiguous uint8 [B,T] the
+    masked scan kernels read.  The conversion runs on the device: no host sync, capture-safe."""
+    if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != (B, T):
+        raise ValueError(f"mask must be a [B,T]=({B},{T}) tensor; got "
+                         f"{tuple(mask.shape) if isinstance(mask, torch.Tensor) else type(mask)}")
+    if mask.device != device:
+        raise ValueError(f"mask is on {mask.device}, the gates are on {device}")
+    if mask.dtype != torch.uint8:
+        mask = (mask != 0).to(torch.uint8)
+    return mask.contiguous()
+
+
+def _scan_fwd(gates, h0, s0, need_ckpt, bias=None, want_h=False, split=False, ln=None, mask=None):
     """split (16-bit gates): out is the first D columns of a [B,T,3D] buffer whose other two
     blocks are out again and h - out (sc_lucy_scan_fwd_split), returned as the last element.
     ln = (ln_r, rec_in, stat, rec_out, eps): the folded LayerNorm (sc_lucy_scan_fwd_ln; ln_r /
-    rec_in None: records out only)."""
+    rec_in None: records out only).  mask: uint8 [B,T] of scan_mask (sc_lucy_scan_fwd_masked: a
+    held frame keeps the state and writes zero); not with ln."""
     require_device(gates, h0, s0)
     if gates.dim() == 4 and gates.shape[2] == 7 and gates.stride(3) != 1:
         gates = gates.contiguous()
     B, T, D, gs = gate_layout(gates)
+    if mask is not None and ln is not None:
+        raise ValueError("the LayerNorm-fold scan has no masked variant")
     if tuple(h0.shape) != (B, D) or tuple(s0.shape) != (B, D):
         raise ValueError(f"h0/s0 must be [B,D]=({B},{D}); got {tuple(h0.shape)}, {tuple(s0.shape)}")
     # the reference reads h0/s0 as contiguous even when handed a strided view (SURVEY F3)
@@ -81,7 +97,14 @@ def _scan_fwd(gates, h0, s0, need_ckpt, bias=None, want_h=False, split=False, ln
     e = gates.element_size()
     nbytes = B * T * D * 8 * e + (ckpt.numel() * 4 if ckpt is not None else 0) + 4 * B * D * 4
     with _timed("lucy_scan_fwd", gates, nbytes):
-        if ln is not None:
+        if mask is not None:
+            rc = lib.sc_lucy_scan_fwd_masked(ptr(gates), dtype_code(gates), ptr(bias), ptr(h0c),
+                                             ptr(s0c), ptr(mask), ptr(out),
+                                             ptr(wide[..., D:2 * D]) if split else None,
+                                             ptr(wide[..., 2 * D:]) if split else None, ptr(s_out),
+                                             ptr(h_out), B, T, D, *gs, out.stride(0), out.stride(1),
+                                             ptr(ckpt), stream_of(gates))
+        elif ln is not None:
             ln_r, rec_in, stat, rec_out, eps = ln
             rc = lib.sc_lucy_scan_fwd_ln(ptr(gates), dtype_code(gates), ptr(bias), ptr(h0c), ptr(s0c),
                                          ptr(out), ptr(wide[..., D:2 * D]) if split else None,
@@ -104,10 +127,15 @@ def _scan_fwd(gates, h0, s0, need_ckpt, bias=None, want_h=False, split=False, ln
     return res + (wide,) if split else res
 
 
-def _scan_bwd(gates, ckpt, dout, ds_last, want_dbias, bias=None, ln=None):
+def _scan_bwd(gates, ckpt, dout, ds_last, want_dbias, bias=None, ln=None, mask=None, dh_last=None):
     """dgates come back in the layout of `gates` (contiguous).  ln = (ln_r, stat): the folded
-    LayerNorm's backward scan (sc_lucy_scan_bwd_ln: dgates = rstd dL/dgate)."""
+    LayerNorm's backward scan (sc_lucy_scan_bwd_ln: dgates = rstd dL/dgate).  mask (the forward's
+    uint8 [B,T]) with dh_last = dL/d h_last (or None): sc_lucy_scan_bwd_masked."""
     B, T, D, gs = gate_layout(gates)
+    if mask is None and dh_last is not None:
+        raise ValueError("dh_last goes to the masked scan only (join it onto dout otherwise)")
+    if dh_last is not None:
+        dh_last = dh_last.to(torch.float32).contiguous()
     if dout is None:
         dout = torch.zeros(B, T, D, dtype=gates.dtype, device=gates.device)
     dout = dout.to(gates.dtype)
@@ -123,7 +151,12 @@ def _scan_bwd(gates, ckpt, dout, ds_last, want_dbias, bias=None, ln=None):
     e = gates.element_size()
     nbytes = B * T * D * 15 * e + ckpt.numel() * 4 + 3 * B * D * 4
     with _timed("lucy_scan_bwd", gates, nbytes):
-        if ln is not None:
+        if mask is not None:
+            rc = _lib.load().sc_lucy_scan_bwd_masked(
+                ptr(gates), dtype_code(gates), ptr(bias), ptr(ckpt), ptr(dout), ptr(ds_last),
+                ptr(dh_last), ptr(mask), ptr(dgates), ptr(dh0), ptr(ds0), ptr(dbias), B, T, D, *gs,
+                dout.stride(0), dout.stride(1), *dgs, stream_of(gates))
+        elif ln is not None:
             rc = _lib.load().sc_lucy_scan_bwd_ln(
                 ptr(gates), dtype_code(gates), ptr(bias), ptr(ckpt), ptr(dout), ptr(ds_last),
                 ptr(dgates), ptr(dh0), ptr(ds0), ptr(dbias), B, T, D, *gs, dout.stride(0),
@@ -146,24 +179,37 @@ class LucyScanFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, gates, h0, s0):
+    def forward(ctx, gates, h0, s0, mask=None):
+        """mask (uint8 [B,T] of scan_mask, or None): the masked scan, which also returns h_last
+        (the state after the last live frame is no longer out[:, -1])."""
         need = any(ctx.needs_input_grad)
-        gates, out, s_out, ckpt = _scan_fwd(gates, h0, s0, need)
+        res = _scan_fwd(gates, h0, s0, need, want_h=mask is not None, mask=mask)
+        gates, out, s_out, ckpt = res[:4]
         if need:
-            ctx.save_for_backward(gates, ckpt)
+            ctx.save_for_backward(gates, ckpt, mask)
             ctx.state_dtypes = (h0.dtype, s0.dtype)
+        if mask is not None:
+            ctx.set_materialize_grads(False)
+            return out, s_out, res[4]
         return out, s_out
 
     @staticmethod
-    def backward(ctx, dout, ds_last):
-        gates, ckpt = ctx.saved_tensors
-        dgates, dh0, ds0, _ = _scan_bwd(gates, ckpt, dout, ds_last, False)
+    def backward(ctx, dout, ds_last, dh_last=None):
+        gates, ckpt, mask = ctx.saved_tensors
+        dgates, dh0, ds0, _ = _scan_bwd(gates, ckpt, dout, ds_last, False, mask=mask,
+                                        dh_last=dh_last)
         hd, sd = ctx.state_dtypes
-        return dgates, dh0.to(hd), ds0.to(sd)
+        res = (dgates, dh0.to(hd), ds0.to(sd))
+        return res if mask is None else res + (None,)
 
 
-def lucy_scan(gates, h0, s0):
-    return LucyScanFn.apply(gates, h0, s0)
+def lucy_scan(gates, h0, s0, mask=None):
+    """(out, s_last) of the scan; with mask [B,T] (nonzero = live) the masked scan's (out, s_last,
+    h_last): a held frame keeps (h, s), writes zero to out and gets zero gradient."""
+    if mask is None:
+        return LucyScanFn.apply(gates, h0, s0)
+    B, T, _, _ = gate_layout(gates)
+    return LucyScanFn.apply(gates, h0, s0, scan_mask(mask, B, T, gates.device))
 
 
 def colsum(x2d, perm=(1, 1)):
@@ -444,8 +490,11 @@ class LucyCellFn(torch.autograd.Function):
     """
 
     @staticmethod
-    def forward(ctx, x2d, w, b, h0, s0, B, T, cdt, imgs=None, split_sink=None, rec_sink=None):
-        """split_sink: a list; when given (bf16), the scan also writes the split-precision planes
+    def forward(ctx, x2d, w, b, h0, s0, B, T, cdt, imgs=None, split_sink=None, rec_sink=None,
+                mask=None):
+        """mask: None, or the uint8 [B,T] of scan_mask: the masked scan (a held frame keeps
+        (h, s) and writes zero; h_last is the state after the last live frame).
+        split_sink: a list; when given (bf16), the scan also writes the split-precision planes
         of its output (sc_lucy_scan_fwd_split) and the [B,T,3D] buffer is appended to it (out is
         its first D columns): the input of CTCHeadFn's one-GEMM fp32-accurate projection.
         rec_sink: a list; when given, the scan also writes its output's LayerNorm block records
@@ -488,7 +537,7 @@ class LucyCellFn(torch.autograd.Function):
             rec = torch.empty(B, T, D // 64, 2, dtype=torch.float32, device=gates.device)
             rec_sink.append(rec)
         res = _scan_fwd(gates, h0, s0, need, bias, want_h=True, split=split_sink is not None,
-                        ln=None if rec is None else (None, None, None, rec, 0.0))
+                        ln=None if rec is None else (None, None, None, rec, 0.0), mask=mask)
         gates, out, s_out, ckpt, h_out = res[:5]
         if len(res) > 5:
             split_sink.append(res[5])
@@ -497,7 +546,7 @@ class LucyCellFn(torch.autograd.Function):
             # the zero-padded copy (sc_gemm_wgrad_bf16, J = 128), and dW keeps the first Din columns
             xw = xg if (USE_WGRAD128 and xg is not xc and xg.shape[1] % 128 == 0
                         and xg.shape[1] % 256 and ctx.needs_input_grad[1]) else xc
-            ctx.save_for_backward(xw, wc, wt, gates, ckpt, bias)
+            ctx.save_for_backward(xw, wc, wt, gates, ckpt, bias, mask)
             ctx.dtypes = (x2d.dtype, w.dtype, h0.dtype, s0.dtype)
             ctx.blocked = blocked
             ctx.din = Din
@@ -505,11 +554,13 @@ class LucyCellFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, ds_last, dh_last):
-        xc, wc, wt, gates, ckpt, bias = ctx.saved_tensors
+        xc, wc, wt, gates, ckpt, bias, mask = ctx.saved_tensors
         xdt, wdt, hdt, sdt = ctx.dtypes
-        dout = _join_dh_last(dout, dh_last, gates)
+        if mask is None:
+            dout = _join_dh_last(dout, dh_last, gates)
+            dh_last = None   # (masked: the kernel takes it, the last live frame is not T - 1)
         dgates, dh0, ds0, dbias = _scan_bwd(gates, ckpt, dout, ds_last, ctx.needs_input_grad[2],
-                                            bias)
+                                            bias, mask=mask, dh_last=dh_last)
         dg2 = dgates.view(xc.shape[0], -1)
         bd = (dg2.shape[1] // 7) if ctx.blocked else 0
         dx = None
@@ -525,18 +576,23 @@ class LucyCellFn(torch.autograd.Function):
                 dw = dw[:, :ctx.din].contiguous()
             dw = dw.to(wdt)
         db = colsum(dbias.view(dbias.shape[0], -1)).to(wdt) if dbias is not None else None
-        return dx, dw, db, dh0.to(hdt), ds0.to(sdt), None, None, None, None, None, None
+        res = (dx, dw, db, dh0.to(hdt), ds0.to(sdt), None, None, None, None, None, None)
+        return res if mask is None else res + (None,)
 
 
-def lucy_cell(x, w, b, h0, s0, cdt=None, imgs=None, split_sink=None, rec_sink=None):
+def lucy_cell(x, w, b, h0, s0, cdt=None, imgs=None, split_sink=None, rec_sink=None, mask=None):
     """x [B,T,Din] -> (out [B,T,D], s_last [B,D] fp32, h_last [B,D] fp32) through projection
     + scan.  imgs: the (forward weight, transposed weight) images of cell_image_spec, or None
-    (the cell casts w itself).  split_sink: see LucyCellFn.forward."""
+    (the cell casts w itself).  split_sink: see LucyCellFn.forward.  mask [B,T] (nonzero = live):
+    the masked scan (held frames keep the state, write zero and get zero gradient)."""
     B, T, Din = x.shape
     if cdt is None:
         cdt = torch.promote_types(x.dtype, w.dtype)
+    if mask is None:
+        return LucyCellFn.apply(x.reshape(B * T, Din), w, b, h0, s0, B, T, cdt, imgs, split_sink,
+                                rec_sink)
     return LucyCellFn.apply(x.reshape(B * T, Din), w, b, h0, s0, B, T, cdt, imgs, split_sink,
-                            rec_sink)
+                            rec_sink, scan_mask(mask, B, T, x.device))
 
 
 # ----------------------------------------------------------------------------- LayerNorm fold ---

@@ -10,6 +10,8 @@ lower-overhead route for eager training.
 
 Reference interfaces (what a ``train.py`` user swaps in):
   lucy_scan   <- rnn_forward_unfused_rmsnorm                        lucyrnn_triton.py:61-73, :180-244
+  lucy_scan_masked <- (planned in the reference's README: "proper input masking") lucy_scan that
+                 holds the state at masked frames
   decay_scan  <- fused_decay_scan                                    lucyrnn_triton.py:158-177
   layer_norm  <- nn.LayerNorm(D) between layers                      lucyrnn_triton.py:96-97, :136-137
   ctc_loss    <- nn.CTCLoss(blank, reduction='mean', zero_infinity)  train.py:142 (on model.py:70's
@@ -37,7 +39,8 @@ OPS = ("abi_version", "lucy_scan_fwd", "lucy_scan_bwd", "decay_scan_fwd", "decay
        "gemm_tn", "gemm_wgrad", "clip_adam_", "rnnt_greedy_decode", "ctc_beam_state_bytes",
        "ctc_beam_reset_", "ctc_beam_frames_", "ctc_beam_result", "ctc_beam_decode",
        "rnnt_beam_state_bytes", "rnnt_beam_reset_", "rnnt_beam_frames_", "rnnt_beam_result",
-       "rnnt_beam_decode", "ctc_align", "wkv_fwd", "wkv_bwd")
+       "rnnt_beam_decode", "ctc_align", "wkv_fwd", "wkv_bwd", "lucy_scan_masked_fwd",
+       "lucy_scan_masked_bwd")
 
 _LOADED = False
 
@@ -82,6 +85,29 @@ def _scan_backward(ctx, dout, ds_last, dh_last, dckpt):
     if want_db:   # per-row partials [B,7,D] -> the bias's [7,D] (logical g*D + d) order
         db = dbias.sum(0).reshape(bias.shape).to(bd)
     return dgates, dh0.to(hd), ds0.to(sd), db, None
+
+
+def _scan_masked_setup(ctx, inputs, output):
+    gates, h0, s0, mask, bias, need_ckpt = inputs
+    ctx.save_for_backward(gates, output[3], mask, bias)
+    ctx.has_bias = bias is not None
+    ctx.dtypes = (h0.dtype, s0.dtype, None if bias is None else bias.dtype)
+
+
+def _scan_masked_backward(ctx, dout, ds_last, dh_last, dckpt):
+    """h_last is the state after the last live frame, not out[:, -1]: its gradient goes to the
+    kernel as the start of the Gh chain."""
+    gates, ckpt, mask, bias = ctx.saved_tensors
+    B, T = gates.shape[:2]
+    D = gates.shape[-1] if gates.dim() == 4 else gates.shape[2] * 64
+    if dout is None:
+        dout = gates.new_zeros(B, T, D)
+    want_db = ctx.has_bias and ctx.needs_input_grad[4]
+    dgates, dh0, ds0, dbias = torch.ops.statecatcher.lucy_scan_masked_bwd(
+        gates, ckpt, dout, mask, ds_last, dh_last, bias, want_db)
+    hd, sd, bd = ctx.dtypes
+    db = dbias.sum(0).reshape(bias.shape).to(bd) if want_db else None
+    return dgates, dh0.to(hd), ds0.to(sd), None, db, None
 
 
 def _decay_setup(ctx, inputs, output):
@@ -205,6 +231,7 @@ def _wkv_backward(ctx, dy, dnum, dden, dmax, dckpt):
 def _register_autograd():
     reg = torch.library.register_autograd
     reg("statecatcher::lucy_scan_fwd", _scan_backward, setup_context=_scan_setup)
+    reg("statecatcher::lucy_scan_masked_fwd", _scan_masked_backward, setup_context=_scan_masked_setup)
     reg("statecatcher::decay_scan_fwd", _decay_backward, setup_context=_decay_setup)
     reg("statecatcher::layer_norm_fwd", _ln_backward, setup_context=_ln_setup)
     reg("statecatcher::ctc_fwd", _ctc_backward, setup_context=_ctc_setup)
@@ -223,6 +250,18 @@ def lucy_scan(gates, h0, s0, gate_bias=None):
     need = torch.is_grad_enabled() and any(
         t is not None and t.requires_grad for t in (gates, h0, s0, gate_bias))
     out, s_last, h_last, _ = sc.lucy_scan_fwd(gates, h0, s0, gate_bias, need)
+    return out, s_last, h_last
+
+
+def lucy_scan_masked(gates, h0, s0, mask, gate_bias=None):
+    """lucy_scan with a per-frame mask [B,T] (nonzero = live; bool, integer or float): a held
+    frame leaves (h, s) untouched, writes zero to out and gets zero gradient, so each row is the
+    scan of its live frames scattered back and (s_last, h_last) is the state after the last live
+    frame."""
+    sc = load()
+    need = torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in (gates, h0, s0, gate_bias))
+    out, s_last, h_last, _ = sc.lucy_scan_masked_fwd(gates, h0, s0, mask, gate_bias, need)
     return out, s_last, h_last
 
 

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Standalone timing of the HIP hot-path kernels at the C2 shape (B=32, T=1500, D=512, V=1024)
 with HIP events, interleaving repetitions in one process.  Prints achieved GB/s against the
-algorithmic bytes of SURVEY §8(d).  usage: python tools/scan_bench.py [--iters N] [--only scan]"""
+algorithmic bytes of SURVEY §8(d).  usage: python tools/scan_bench.py [--iters N] [--only scan]
+--mask {ones,tail30,random} (with --only scan): the masked scan kernels against the unmasked ones
+on the same gates, the two alternated round by round in this process; min, median and max of the
+rounds are printed for both (the spread is the yardstick for the difference)."""
 import argparse
 import os
 import sys
@@ -15,6 +18,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--only", default="all")
 ap.add_argument("--dtype", default="bf16")
+ap.add_argument("--mask", default="none", choices=["none", "ones", "tail30", "random"])
+ap.add_argument("--rounds", type=int, default=7)
 args = ap.parse_args()
 dt = {"bf16": torch.bfloat16, "fp32": torch.float32, "fp16": torch.float16}[args.dtype]
 dev = "cuda"
@@ -41,6 +46,43 @@ def timeit(fn, iters, rounds=5):
     return best
 
 
+def alternate(arms, iters, rounds):
+    """{name: sorted per-round mean seconds}: the arms run one after the other inside each round."""
+    for fn in arms.values():
+        for i in range(5):
+            fn(i)
+    torch.cuda.synchronize()
+    out = {k: [] for k in arms}
+    for _ in range(rounds):
+        for k, fn in arms.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(iters):
+                fn(i)
+            e1.record()
+            torch.cuda.synchronize()
+            out[k].append(e0.elapsed_time(e1) / iters * 1e-3)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def report_arms(name, res):
+    base = res["unmasked"][len(res["unmasked"]) // 2]
+    for k, v in res.items():
+        med = v[len(v) // 2]
+        print(f"{name:24s} {k:9s} min {v[0] * 1e6:8.1f}  median {med * 1e6:8.1f}  max {v[-1] * 1e6:8.1f} us"
+              f"  ({(med / base - 1) * 100:+.2f}% of the unmasked median)", flush=True)
+
+
+def make_mask(kind):
+    m = torch.ones(B, T, dtype=torch.uint8, device=dev)
+    if kind == "tail30":   # ragged: the rows lose up to 60% of their frames, 30% on average
+        lens = torch.linspace(0.4, 1.0, B, device=dev).mul(T).long()
+        m = (torch.arange(T, device=dev)[None, :] < lens[:, None]).to(torch.uint8)
+    elif kind == "random":
+        m = (torch.rand(B, T, device=dev) < 0.7).to(torch.uint8)
+    return m.contiguous()
+
+
 def report(name, sec, nbytes):
     print(f"{name:28s} {sec * 1e6:9.1f} us  {nbytes / sec / 1e9:8.1f} GB/s  "
           f"{nbytes / sec / 8e12 * 100:5.1f}% of 8 TB/s", flush=True)
@@ -60,6 +102,22 @@ if args.only in ("all", "scan"):
             gs.append(g if lay == "plain" else g.view(B, T, 7, D // 64, 64).permute(0, 1, 3, 2, 4).contiguous())
         fw = [ops._scan_fwd(g, h0, s0, True, bias) for g in gs]
         ck = fw[0][3]
+        if args.mask != "none":
+            mk = make_mask(args.mask)
+            print(f"mask {args.mask}: {float(mk.float().mean()) * 100:.1f}% live frames", flush=True)
+            fm = [ops._scan_fwd(g, h0, s0, True, bias, mask=mk) for g in gs]
+            report_arms(f"scan_fwd {args.dtype} {lay}", alternate({
+                "unmasked": lambda i: ops._scan_fwd(gs[i % NROT], h0, s0, True, bias),
+                "masked": lambda i: ops._scan_fwd(gs[i % NROT], h0, s0, True, bias, mask=mk),
+            }, args.iters, args.rounds))
+            report_arms(f"scan_bwd {args.dtype} {lay}", alternate({
+                "unmasked": lambda i: ops._scan_bwd(gs[i % NROT], fw[i % NROT][3], dout[i % NROT], None,
+                                                    True, bias),
+                "masked": lambda i: ops._scan_bwd(gs[i % NROT], fm[i % NROT][3], dout[i % NROT], None,
+                                                  True, bias, mask=mk),
+            }, args.iters, args.rounds))
+            del gs, fw, fm
+            continue
         nb_f = B * T * D * 8 * e + ck.numel() * 4
         report(f"lucy_scan_fwd {args.dtype} {lay}",
                timeit(lambda i: ops._scan_fwd(gs[i % NROT], h0, s0, True, bias), args.iters), nb_f)
